@@ -14,6 +14,11 @@ share per document replaced by a random G2 point (1/64 invalid).  Keys and share
 on the GPU with the engine's own scalar-multiplication kernels; verdicts are checked against the
 construction.
 
+A plain run (--gpus 1 --steps K --warmup W) sets up, warms up, times the K steps and prints the
+line.  --full adds what takes runs of its own: the isolated-launch roofline, the whole node from
+wire bytes, the combine latency, the decoder rates and the CPU baseline.  --dump-outputs DIR writes
+the last timed step's outputs as .npy files.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -460,7 +465,29 @@ def decode_rate(eng, w, n):
             "g1_decode_ms_device": dev1_ms, "decode_points": n}
 
 
-def from_wire(eng, w, n, streams, steps, warmup, world, dev, d_pk, d_hs, d_di, to_dev):
+DUMP_LIMIT = 60 << 20   # bytes of .npy data per --dump-outputs directory (under 64 MB with the headers)
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs DIR: what the timed path's last step handed back, one DIR/<name>.npy per array
+    (<name>.rank<r>.npy with several ranks).  Bytes are written as float32, 32-bit words as float64
+    (both exact).  When the arrays together exceed DUMP_LIMIT, one over its equal share of it is cut to
+    a fixed seeded sample of its elements, in order, so two builds given the same arguments write
+    comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a).astype(np.float32 if a.dtype.itemsize == 1 else np.float64).ravel()
+              for name, a in arrays.items()}
+    fits = sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    share = DUMP_LIMIT // max(1, len(arrays))
+    for name, a in arrays.items():
+        if not fits and a.nbytes > share:
+            keep = np.random.default_rng(20261016).choice(a.size, share // a.itemsize, replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(dirname, name + (".rank%d" % rank if world > 1 else "") + ".npy"), a)
+
+
+def from_wire(eng, w, n, streams, steps, warmup, world, dev, d_pk, d_hs, d_di, to_dev, full=True, dump=None,
+              rank=0):
     """The whole node from wire bytes: each step takes the batch's n signature
     shares as the 96-byte compressed encodings a node receives (threshold_sign::Message,
     src/threshold_sign.rs:73; the Message's bincode framing is host work, wire.py) already in HBM,
@@ -502,7 +529,16 @@ def from_wire(eng, w, n, streams, steps, warmup, world, dev, d_pk, d_hs, d_di, t
         d_v[j].zero_()
         d_sg[j].zero_()
     ms = timed_steps(step, streams, steps, world, dev)
+    if dump:  # the last timed step's buffers: decoded points (as 32-bit words), decode flags, verdicts
+        j = (steps - 1) % len(streams)
+        dump_outputs(dump, {"decoded_points": d_sg[j].cpu().numpy().view(np.uint32), "decode_ok": d_ok[j].cpu().numpy(),
+                            "verdicts": d_v[j].cpu().numpy()}, rank, world)
     ok = ok and outputs_ok(min(steps, len(streams)))
+    line = {"value": n * world / (ms / 1e3), "unit": "shares/s", "ms_per_step": ms, "steps": steps,
+            "outputs_ok": ok,
+            "input": "%d compressed 96-byte signature shares in HBM per step (%d documents)" % (n, nh)}
+    if not full:
+        return line
     eng.set_profiling(True)
     for _ in range(3):
         step(0)
@@ -511,12 +547,11 @@ def from_wire(eng, w, n, streams, steps, warmup, world, dev, d_pk, d_hs, d_di, t
     pair_ms, pair_n = eng.stage_time(STAGE_PAIRING)
     eng.set_profiling(False)
     dec_avg = dec_ms / max(dec_n, 1)
-    return {"value": n * world / (ms / 1e3), "unit": "shares/s", "ms_per_step": ms, "steps": steps,
-            "outputs_ok": ok, "decode_ms_isolated": dec_avg, "verify_ms_isolated": pair_ms / max(pair_n, 1),
-            "kernels": [roofline_entry("hb::k_g2_decompress", dec_n, dec_avg, n, workcount.WIRE_G2_DECODE,
-                                       "compressed G2 point (flags, sqrt, subgroup)",
-                                       n / 64 / 1024, source="sign")],
-            "input": "%d compressed 96-byte signature shares in HBM per step (%d documents)" % (n, nh)}
+    line.update({"decode_ms_isolated": dec_avg, "verify_ms_isolated": pair_ms / max(pair_n, 1),
+                 "kernels": [roofline_entry("hb::k_g2_decompress", dec_n, dec_avg, n, workcount.WIRE_G2_DECODE,
+                                            "compressed G2 point (flags, sqrt, subgroup)",
+                                            n / 64 / 1024, source="sign")]})
+    return line
 
 
 def main():
@@ -525,10 +560,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=NDOCS * N_NODES)
+    ap.add_argument("--full", action="store_true",
+                    help="sign workload: beside the headline figure also measure the isolated-launch roofline, the "
+                         "whole node from wire bytes, the combine latency, the decoders and the CPU baseline "
+                         "(each has its --no-... switch); without it the run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the verdicts; with "
+                         "--from-wire also the decoded points and decode flags) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-combine", action="store_true")
+    ap.add_argument("--no-combine", action="store_true", help="with --full: skip the combine latency and decoder rates")
     ap.add_argument("--no-wire", action="store_true",
-                    help="sign workload: skip the whole-node-from-wire-bytes line (decode + verify per step)")
+                    help="with --full: skip the whole-node-from-wire-bytes line (decode + verify per step)")
     ap.add_argument("--from-wire", action="store_true",
                     help="sign workload: the line's value is the whole node from wire bytes (compressed shares "
                          "decoded on the device inside every timed step) instead of device-resident points")
@@ -576,6 +619,10 @@ def main():
                          "(SyncKeyGen N=100 t=33 ack checks of one node); epoch = configs[4] (HoneyBadger N=100 f=33 "
                          "epoch crypto of one node)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload == "epoch":
+        ap.error("--dump-outputs covers the sign, decrypt and dkg workloads")
     rc = launch(args)
     if rc is not None:
         sys.exit(rc)
@@ -637,35 +684,32 @@ def main():
         d.zero_()
     ms_step = timed_steps(step, streams, args.steps, world, dev)
     value = n * world / (ms_step / 1e3)
+    if args.dump_outputs and not args.from_wire:
+        dump_outputs(args.dump_outputs, {"verdicts": d_vs[(args.steps - 1) % len(streams)].cpu().numpy()}, rank, world)
     ok = ok and verdicts_ok(min(args.steps, len(streams)))
-    # roofline: isolated launches on one stream (no overlap), HIP events around each launch
-    eng.set_profiling(True)
-    for _ in range(max(2, min(args.steps, 5))):
-        step(0)
-    torch.cuda.synchronize(dev)
-    pair_ms, pair_n = eng.stage_time(STAGE_PAIRING)
-    prep_ms, prep_n = eng.stage_time(STAGE_PREPARE)
-    eng.set_profiling(False)
-    ok = ok and verdicts_ok()
-    per_rank = gather_per_rank({"rank": rank, "device": local, "kernel_ms": pair_ms / max(pair_n, 1),
-                                "ms_per_step": ms_step, "verdicts_ok": ok}, world)
+    mine = {"rank": rank, "device": local, "ms_per_step": ms_step}
+    if args.full:
+        # roofline: isolated launches on one stream (no overlap), HIP events around each launch
+        eng.set_profiling(True)
+        for _ in range(max(2, min(args.steps, 5))):
+            step(0)
+        torch.cuda.synchronize(dev)
+        pair_ms, pair_n = eng.stage_time(STAGE_PAIRING)
+        prep_ms, prep_n = eng.stage_time(STAGE_PREPARE)
+        eng.set_profiling(False)
+        ok = ok and verdicts_ok()
+        mine["kernel_ms"] = pair_ms / max(pair_n, 1)
+    per_rank = gather_per_rank(dict(mine, verdicts_ok=ok), world)
     ok = all(r["verdicts_ok"] for r in per_rank)
     wire = None
-    if args.from_wire or not args.no_wire:
-        wire = from_wire(eng, w, n, streams, max(2, args.steps if args.from_wire else min(args.steps, 5)),
-                         args.warmup, world, dev, d_pk, d_hs, d_di, to_dev)
+    if args.from_wire or (args.full and not args.no_wire):
+        # --from-wire: the line's own figure, all --steps of it; otherwise a short line beside it
+        wire = from_wire(eng, w, n, streams, args.steps if args.from_wire else max(2, min(args.steps, 5)),
+                         args.warmup, world, dev, d_pk, d_hs, d_di, to_dev, full=args.full,
+                         dump=args.dump_outputs if args.from_wire else None, rank=rank)
         ok = ok and wire["outputs_ok"]
 
     if rank == 0:
-        kern_ms = pair_ms / max(pair_n, 1)
-        main_k = roofline_entry(KERNEL_NAMES[args.impl], pair_n, kern_ms, n, workcount.PAIR_CHECK_WALK, "share check",
-                                pair_waves_per_simd(n, {"quad": 4, "oct": 8}.get(args.impl, 2))
-                                if args.impl in ("pair", "auto", "quad", "oct") else None)
-        kernels = [main_k]
-        if prep_n:
-            kernels.append(roofline_entry("hbs::k_oct_prep" if args.impl in ("pair", "auto", "quad", "oct") else "hb::k_g2_prepare",
-                                          prep_n, prep_ms / prep_n, nh, workcount.PAIR_PREP_DOC, "document (G2 walk)",
-                                          nh * 8 / 64 / 1024))  # one lane octo per point
         out = {
             "metric": METRIC, "value": value, "unit": "shares/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -675,27 +719,42 @@ def main():
                        "streams": len(streams),
                        "documents_per_gpu": nh, "n_nodes": N_NODES, "f": F_FAULTY, "pairing_impl": args.impl,
                        "parallelism": "shard-by-batch x%d" % world},
-            "verdicts_ok": ok, "per_rank": per_rank, "reference_work": reference_work(main_k, workcount),
+            "verdicts_ok": ok, "per_rank": per_rank,
+        }
+    if rank == 0 and args.full:
+        kern_ms = pair_ms / max(pair_n, 1)
+        main_k = roofline_entry(KERNEL_NAMES[args.impl], pair_n, kern_ms, n, workcount.PAIR_CHECK_WALK, "share check",
+                                pair_waves_per_simd(n, {"quad": 4, "oct": 8}.get(args.impl, 2))
+                                if args.impl in ("pair", "auto", "quad", "oct") else None)
+        kernels = [main_k]
+        if prep_n:
+            kernels.append(roofline_entry("hbs::k_oct_prep" if args.impl in ("pair", "auto", "quad", "oct") else "hb::k_g2_prepare",
+                                          prep_n, prep_ms / prep_n, nh, workcount.PAIR_PREP_DOC, "document (G2 walk)",
+                                          nh * 8 / 64 / 1024))  # one lane octo per point
+        out.update({
+            "reference_work": reference_work(main_k, workcount),
             "roofline": dict(main_k, bound="valu-int", unit="T MAD/s (v_mad_u64_u32 32x32->64)",
                              **traffic_fields(KERNEL_NAMES[args.impl], "sign"), kernels=kernels,
                              note="achieved = checks x algorithmic MADs per check (workcount.PAIR_CHECK_WALK: "
                                   "2-pair Miller + sigma G2 walk + final exp; 300 MAD/Fp-mul, 222/Fp-sqr) / "
                                   "average launch time of isolated single-stream launches (the throughput value alternates two "
                                   "streams); peak = measured MAD rate at 8 waves/SIMD"),
-        }
+        })
+    if rank == 0:
         if wire is not None:
             out["whole_node_from_wire"] = wire
             if args.from_wire:
                 out["value"], out["ms_per_step"] = wire["value"], wire["ms_per_step"]
-                out["roofline"]["kernels"] = out["roofline"]["kernels"] + wire["kernels"]
+                if args.full:
+                    out["roofline"]["kernels"] = out["roofline"]["kernels"] + wire["kernels"]
                 out["config"]["workload"] += ", from compressed wire bytes (decode + verify per step)"
-        if not args.no_combine:
+        if args.full and not args.no_combine:
             lat, rate, dev_rate = combine_latency(eng, w)
             out["combine_latency_ms"] = lat
             out["combines_per_s_batched"] = rate          # host-to-host, 1,024 combines in one call
             out["combines_per_s_batched_device"] = dev_rate  # k_interp_endo time only
             out.update(decode_rate(eng, w, n))  # hbh_g2/g1_decompress: host-to-host and kernel-only rates
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out), flush=True)
     eng.close()
@@ -774,6 +833,9 @@ def run_decrypt(args, eng, world, rank, dev):
     for d in d_vs:      # the timed steps must write every verdict again
         d.zero_()
     ms_step = timed_steps(step, streams, args.steps, world, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts": d_vs[(args.steps - 1) % len(streams)].cpu().numpy()[:n]},
+                     rank, world)
     ok = ok and verdicts_ok(min(args.steps, len(streams)))
     from hbbft_amd._lib import STAGE_PAIRING, STAGE_PREPARE
     eng.set_profiling(True)   # roofline: isolated single-stream launches
@@ -941,6 +1003,8 @@ def run_dkg(args, eng, world, rank, dev):
         ok = ok and v == expected
     dev_ms, dev_n = eng.stage_time(STAGE_CURVE)
     eng.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts": np.frombuffer(bytes(v), dtype=np.uint8)}, rank, world)
     dev_ms /= max(dev_n, 1)
     nack = len(vals)
     # row build (once per (part, x), cached in the set) timed separately on a fresh set
@@ -1401,6 +1465,8 @@ def run_pool(args):
     for _ in range(args.steps):
         step()
     ms_step = (time.perf_counter() - t0) * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts": np.frombuffer(bytes(out), dtype=np.uint8)})
     ok = ok and verdicts_ok()
     engines = [pool.shard_engine(s) for s in range(nsh)]
     for e in engines:

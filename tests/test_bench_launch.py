@@ -37,10 +37,55 @@ def test_pool_over_absent_devices_exits_nonzero():
     assert r.returncode == 2
 
 
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"], {})
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
+
+
 def _json_line(out):
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out
     return json.loads(lines[0])
+
+
+FULL_ONLY = ("roofline", "reference_work", "whole_node_from_wire", "combine_latency_ms", "g2_decode_per_s",
+             "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline fields only; --dump-outputs
+    writes the last timed step's verdicts (float32, one per check): 1/64 invalid by construction
+    (check m * 64 + (m * 37) % 64 of document m), the same file from a second run."""
+    import numpy as np
+    dumps = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--batch", "4096", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                  str(tmp_path / d)], {}, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == 3 and line["verdicts_ok"] is True and line["higher_is_better"] is True
+        assert line["unit"] == "shares/s" and line["ms_per_step"] > 0
+        assert abs(line["value"] - 4096 / (line["ms_per_step"] / 1e3)) <= 1e-6 * line["value"]
+        assert not [k for k in FULL_ONLY if k in line]
+        assert os.listdir(tmp_path / d) == ["verdicts.npy"]
+        dumps.append(np.load(tmp_path / d / "verdicts.npy"))
+    want = np.ones(4096, dtype=np.float32)
+    want[[m * 64 + (m * 37) % 64 for m in range(64)]] = 0
+    assert dumps[0].dtype == np.float32 and (dumps[0] == want).all() and (dumps[1] == want).all()
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_other_measurements(tmp_path):
+    """--full: the roofline, the from-wire line, the combine latency and the decoder rates beside the
+    headline figure (the CPU baseline, a 12-second sample, is switched off here)."""
+    r = _run(["--gpus", "1", "--batch", "4096", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+             {}, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["verdicts_ok"] is True and line["whole_node_from_wire"]["outputs_ok"] is True
+    assert [k for k in FULL_ONLY if k not in line] == ["cpu_baseline"]
+    assert line["roofline"]["avg_launch_ms"] > 0 and line["per_rank"][0]["kernel_ms"] > 0
 
 
 @pytest.mark.gpu

@@ -37,7 +37,7 @@ if [ "${PART:-a}" = "a" ]; then
   for d in $O/pmc_*/; do python3 tools/pmc_summary.py $d > $d/summary.txt; done
   tail -12 $O/pmc_traffic.txt
 else
-  for S in ${LINES:-"sign:" "sign_wire:--from-wire" "decrypt:--workload decrypt" "dkg:--workload dkg" "epoch:--workload epoch" "epoch_raw:--workload epoch --raw"}; do
+  for S in ${LINES:-"sign:--full" "sign_wire:--full --from-wire" "decrypt:--workload decrypt" "dkg:--workload dkg" "epoch:--workload epoch" "epoch_raw:--workload epoch --raw"}; do
     W=${S%%:*}; A=${S#*:}
     timeout -k 10 600 python3 -u bench.py $A > $O/bench_$W.json 2> $O/bench_$W.err || { tail -5 $O/bench_$W.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/bench_$W.json')); r=d.get('roofline',{}); print('$W', round(d['value'],1), d['unit'], 'ms/step', round(d['ms_per_step'],3), 'frac', round(r.get('frac',0),4), 'match', (r.get('traffic_source') or {}).get('matches_loaded_lib'))"
@@ -49,7 +49,7 @@ else
   tail -1 $O/decode_65536.txt
   cd /tmp
   mkdir -p $O/default_bench
-  timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default_bench -o run -- python3 $R/bench.py --steps 5 --warmup 2 > $O/default_bench/run.log 2>&1 || { echo "default trace failed"; tail -5 $O/default_bench/run.log; exit 1; }
+  timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default_bench -o run -- python3 $R/bench.py --full --steps 5 --warmup 2 > $O/default_bench/run.log 2>&1 || { echo "default trace failed"; tail -5 $O/default_bench/run.log; exit 1; }
   head -8 $O/default_bench/run_kernel_stats.csv | cut -c1-150
 fi
 echo done
