@@ -49,6 +49,7 @@ SIGNATURES = [
     ("hbh_bivar_ack_check_set", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
     ("hbh_engine_set_pairing_impl", _I, [_P, _I]),
     ("hbh_engine_set_ack_impl", _I, [_P, _I]),
+    ("hbh_engine_set_decode_impl", _I, [_P, _I]),
     ("hbh_engine_set_profiling", _I, [_P, _I]),
     ("hbh_engine_stage_time", _I, [_P, _I, _c.POINTER(_c.c_double), _c.POINTER(_I)]),
     # device-resident variants
@@ -88,6 +89,8 @@ SIGNATURES = [
 STAGE_PREPARE, STAGE_PAIRING, STAGE_CURVE = 0, 1, 2
 IMPL_AUTO, IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT, IMPL_WAVE2 = 3, 4, 5, 6, 7, 8   # HBH_IMPL_* (0, 1, 2 = retired THREAD, LANE_COOP, THREAD_SIGNED)
 ACK_AUTO, ACK_QUAD, ACK_LANE, ACK_LANE_HORNER = 0, 1, 2, 3  # HBH_ACK_*
+DEC_AUTO, DEC_LANE, DEC_SPLIT = 0, 1, 2  # HBH_DEC_*
+AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPLIT_MAX
 
 _lib = None
 

@@ -99,6 +99,7 @@ struct hbh_engine {
   bool profiling = false;
   int impl = HBH_IMPL_AUTO;  // pairing implementation (hbh_engine_set_pairing_impl)
   int ack_impl = HBH_ACK_AUTO;  // Ack-check kernel of commitment sets (hbh_engine_set_ack_impl)
+  int dec_impl = HBH_DEC_AUTO;  // point-decoding kernels (hbh_engine_set_decode_impl)
   StageTimer timer;
   // Completion of the last call's device work on whichever stream it ran.  Every call waits for it
   // on its own stream before touching the engine-owned workspaces, so a _dev call on a caller
@@ -538,6 +539,15 @@ int hbh_engine_set_ack_impl(hbh_engine* e, int impl) {
     return fail(HBH_ERR_ARG, "unknown Ack-check implementation");
   std::lock_guard<std::mutex> lk(e->mu);
   e->ack_impl = impl;
+  return HBH_OK;
+}
+
+int hbh_engine_set_decode_impl(hbh_engine* e, int impl) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (impl != HBH_DEC_AUTO && impl != HBH_DEC_LANE && impl != HBH_DEC_SPLIT)
+    return fail(HBH_ERR_ARG, "unknown point-decoding implementation");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->dec_impl = impl;
   return HBH_OK;
 }
 
@@ -1227,6 +1237,18 @@ void parse_compressed(const uint8_t* b, int nfe, uint32_t* words, uint8_t& f) {
   }
 }
 
+// The decoder of one call: a forced form for every n; AUTO takes the latency form (k_wire_split.hip)
+// up to the group's threshold and the throughput form (k_wire.hip) above it.
+hipError_t launch_decompress(const hbh_engine* e, hipStream_t s, size_t n, bool g2, const uint32_t* xw,
+                             const uint8_t* fl, void* out, uint8_t* ok) {
+  const size_t split_max = g2 ? HBH_AUTO_DEC_G2_SPLIT_MAX : HBH_AUTO_DEC_G1_SPLIT_MAX;
+  const bool split = e->dec_impl == HBH_DEC_SPLIT || (e->dec_impl == HBH_DEC_AUTO && n <= split_max);
+  if (g2)
+    return split ? hbl::g2_decompress_split(s, (int)n, xw, fl, out, ok)
+                 : hbl::g2_decompress(s, (int)n, xw, fl, out, ok);
+  return split ? hbl::g1_decompress_split(s, (int)n, xw, fl, out, ok) : hbl::g1_decompress(s, (int)n, xw, fl, out, ok);
+}
+
 int run_decompress(hbh_engine* e, size_t n, const uint8_t* in, uint8_t* out, uint8_t* ok, bool g2) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n == 0) return HBH_OK;
@@ -1251,12 +1273,8 @@ int run_decompress(hbh_engine* e, size_t n, const uint8_t* in, uint8_t* out, uin
   HBH_CHECK(hipMemcpyAsync(e->in_a.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice, s));
   HBH_CHECK(hipMemcpyAsync(e->in_b.p, fl.data(), n, hipMemcpyHostToDevice, s));
   hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  if (g2)
-    HBH_CHECK(hbl::g2_decompress(s, (int)n, (const uint32_t*)e->in_a.p, (const uint8_t*)e->in_b.p, e->out_x.p,
-                                 (uint8_t*)e->out_v.p));
-  else
-    HBH_CHECK(hbl::g1_decompress(s, (int)n, (const uint32_t*)e->in_a.p, (const uint8_t*)e->in_b.p, e->out_x.p,
-                                 (uint8_t*)e->out_v.p));
+  HBH_CHECK(launch_decompress(e, s, n, g2, (const uint32_t*)e->in_a.p, (const uint8_t*)e->in_b.p, e->out_x.p,
+                              (uint8_t*)e->out_v.p));
   e->timer.end(s, tm);
   HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, n * pb, hipMemcpyDeviceToHost, s));
   HBH_CHECK(hipMemcpyAsync(ok, e->out_v.p, n, hipMemcpyDeviceToHost, s));
@@ -1444,10 +1462,7 @@ int run_decompress_dev(hbh_engine* e, void* stream, size_t n, const uint8_t* d_i
   uint8_t* fl = (uint8_t*)e->wire_f[slot].p;
   hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
   HBH_CHECK(hbl::wire_parse(s, (int)n, nfe, d_in, xw, fl));
-  if (g2)
-    HBH_CHECK(hbl::g2_decompress(s, (int)n, xw, fl, d_out, d_ok));
-  else
-    HBH_CHECK(hbl::g1_decompress(s, (int)n, xw, fl, d_out, d_ok));
+  HBH_CHECK(launch_decompress(e, s, n, g2, xw, fl, d_out, d_ok));
   e->timer.end(s, tm);
   HBH_CHECK(hipEventRecord(e->wire_done[slot], s));
   return HBH_OK;

@@ -10,20 +10,13 @@
 
 #include "curve.hpp"
 #include "wire.hpp"
-#include "sqrt_chain.inc"
+#include "wire_root.hpp"
 
 #ifndef HBH_G1_WAVES_PER_SIMD
 #define HBH_G1_WAVES_PER_SIMD 2  // A/B: 1 (512 registers, no spills, half the waves in flight)
 #endif
 
 namespace hb {
-
-// canonical words a > b
-__device__ __forceinline__ bool words_gt(const uint32_t* a, const uint32_t* b, int n) {
-  for (int i = n - 1; i >= 0; i--)
-    if (a[i] != b[i]) return a[i] > b[i];
-  return false;
-}
 
 // ---------------------------------------------------------------------------- subgroup membership
 // Endomorphism tests instead of r * P == O (255-bit double-and-add):
@@ -120,19 +113,7 @@ __global__ void __launch_bounds__(128, HBH_G1_WAVES_PER_SIMD) k_g1_decompress(in
     valid = true;  // the point at infinity (all-zero ABI words)
     for (int k = 0; k < 12; k++) x[k] = 0;
   } else if (try_point) {  // the square root, beside the other wave's subgroup test
-    Fp ym = fp_mul(rhs, fp_pow_pm3d4(rhs));  // rhs^((p+1)/4)
-    if (fp_eq(fp_sqr(ym), rhs)) {
-      // "greatest" = y > p - y, i.e. y > (p - 1) / 2
-      fp_to_words(ym, y);
-      uint32_t half[12];
-      for (int k = 0; k < 12; k++) half[k] = (p[k] >> 1) | (k < 11 ? (p[k + 1] << 31) : 0u);
-      const bool greatest = words_gt(y, half, 12);
-      if (greatest != ((f & hbl::WIRE_GREATEST) != 0)) {
-        ym = fp_neg(ym);
-        fp_to_words(ym, y);
-      }
-      valid = true;  // on the curve; the subgroup verdict joins after the barrier
-    }
+    valid = g1_root_y(rhs, f, p, y);  // on the curve; the subgroup verdict joins after the barrier
   }
   __syncthreads();
   if (role == 1 || !live) return;
@@ -143,44 +124,6 @@ __global__ void __launch_bounds__(128, HBH_G1_WAVES_PER_SIMD) k_g1_decompress(in
     o[12 + k] = valid ? y[k] : 0u;
   }
   ok[i] = valid ? 1 : 0;
-}
-
-// pairing 0.14 Ord for Fq2: c1 first, then c0 (canonical integers)
-__device__ __forceinline__ bool f2_gt_canon(const Fp2& a, const Fp2& b) {
-  uint32_t a0[12], a1[12], b0[12], b1[12];
-  fp_to_words(a.c0, a0);
-  fp_to_words(a.c1, a1);
-  fp_to_words(b.c0, b0);
-  fp_to_words(b.c1, b1);
-  bool eq1 = true;
-  for (int k = 0; k < 12; k++) eq1 = eq1 && a1[k] == b1[k];
-  return eq1 ? words_gt(a0, b0, 12) : words_gt(a1, b1, 12);
-}
-
-// Square root in Fp2 by the norm (two Fp exponentiations by (p-3)/4 instead of two Fp2 ones):
-// a = a0 + a1 u is a square iff N = a0^2 + a1^2 is a square in Fp; with s = sqrt(N) and
-// t = (a0 + s) / 2 (or (a0 - s) / 2 when that is 0), w = t^((p-3)/4):
-//   t w^2 ==  1 (t a square):      y = t w + (a1 w / 2) u
-//   t w^2 == -1 (-t a square; p = 3 mod 8 makes (-1)^((p-3)/4) = 1, so w serves -t too):
-//                                  y = a1 w / 2 - (t w) u
-// (t (a0 - s)/2 = -a1^2 / 4 is a non-square for a1 != 0, so exactly one case holds.)  Any root:
-// the caller picks the sign.  false when a is not a square.
-__device__ __forceinline__ bool f2_sqrt_norm(const Fp2& a, Fp2& out) {
-  out = f2_zero();
-  if (f2_is_zero(a)) return true;
-  const Fp nrm = fp_add(fp_sqr(a.c0), fp_sqr(a.c1));
-  const Fp s = fp_mul(nrm, fp_pow_pm3d4(nrm));
-  if (!fp_eq(fp_sqr(s), nrm)) return false;
-  const Fp half = fp_const(INV2_M);
-  Fp t = fp_mul(fp_add(a.c0, s), half);
-  if (fp_is_zero(t)) t = fp_mul(fp_sub(a.c0, s), half);
-  const Fp w = fp_pow_pm3d4(t);
-  const Fp tw = fp_mul(t, w);
-  const Fp aw = fp_mul(fp_mul(a.c1, half), w);
-  const bool qr = fp_eq(fp_mul(tw, w), fp_one());
-  const Fp2 y = qr ? Fp2{tw, aw} : Fp2{aw, fp_neg(tw)};
-  out = y;
-  return f2_is_zero(f2_sub(f2_sqr(y), a));
 }
 
 // G2: two waves per 64 points, as G1.  The subgroup test needs y only through its norm: with
@@ -238,9 +181,7 @@ __global__ void __launch_bounds__(128, WPS) k_g2_decompress(int n, const uint32_
     const Fp2 xm = {fp_from_words(xi), fp_from_words(xi + 12)};
     const Fp2 rhs = f2_add(f2_mul(f2_sqr(xm), xm), b2);
     Fp2 ym;
-    if (f2_sqrt_norm(rhs, ym)) {
-      const Fp2 ny = f2_neg(ym);
-      if (f2_gt_canon(ym, ny) != ((f & hbl::WIRE_GREATEST) != 0)) ym = ny;
+    if (g2_root_y(rhs, f, ym)) {
       const Fp nm = fp_add(fp_sqr(ym.c0), fp_sqr(ym.c1));
       for (int k = 0; k < NL; k++) nrm[k * 64 + lane] = nm.l[k];
       // on the curve: written now, zeroed after the second barrier when not in the subgroup

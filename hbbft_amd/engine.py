@@ -347,6 +347,13 @@ class Engine:
         dense y runs), 3 = one lane per ack, Horner only (commitment sets)."""
         check(self._l.hbh_engine_set_ack_impl(self._h, int(impl)))
 
+    def set_decode_impl(self, impl):
+        """HBH_DEC_*: 0 = auto (default: the latency form up to AUTO_DEC_G1_SPLIT_MAX /
+        AUTO_DEC_G2_SPLIT_MAX points per call), 1 = one lane per point's subgroup chain (throughput),
+        2 = four lanes per point's subgroup chain (latency).  Governs g1/g2_decompress and their _dev
+        forms; both forms write the same bytes."""
+        check(self._l.hbh_engine_set_decode_impl(self._h, int(impl)))
+
     # ------------------------------------------------------------ profiling
     def set_profiling(self, on):
         check(self._l.hbh_engine_set_profiling(self._h, 1 if on else 0))

@@ -146,3 +146,51 @@ WIRE_G1_DECODE = _add((1, 0), (2, 1), SQRT_CHAIN, (2, 1), (1, 0), (2, 1),
 WIRE_G2_DECODE = _add((2, 0), (F2S + F2M, 0), (2, 2), _scale(SQRT_CHAIN, 2), (1, 0), (1, 1), (1, 0),
                       (1, 0), (2, 0), (1, 0), (F2S, 0), (6, 0),
                       _scale(G2_DBL, NBITS), _scale(G2_MADD, NADD), (2 + F2M, 0), (F2S + 3 * F2M, 0))
+
+
+# ---------------------------------------------------------------------------- wire decoding, per role
+# Both decoder forms run two roles side by side in one workgroup, so a small batch takes the longer
+# role's serial chain.  Critical paths below are in Fp-product times: one lane's Fp product = 1, a
+# round of lane-quad products = 1 (g1quad.hpp: every lane forms one Fp product), a round of
+# lane-pair products = 1.5 (pfp.hpp h_mul: 588 multiply-adds per lane against 392 for an Fp product).
+WIRE_ROOT_G1 = 1 + 2 + SQRT_CHAIN[0] + 2 + 1            # to Montgomery, x^3 + 4, chain, y and its check, canonical y
+WIRE_ROOT_G2 = (2 + (F2S + F2M) + 2 + 2 * SQRT_CHAIN[0]  # to Montgomery, x^3 + b, norm, two dependent chains,
+                + 1 + 1 + 1 + 1 + 2 + 1 + F2S + 6 + 2)  # s, s^2, t, t w, a1 w / 2, t w^2, y^2, sign compare, N(y)
+# HBH_DEC_LANE (k_wire.hip): one lane runs the whole [|x|] chain(s)
+WIRE_LANE_SUB_G1 = 1 + 2 + 2 + 2 * NBITS * G1_DBL[0] + NADD * (G1_MADD[0] + G1_ADD[0]) + 5
+WIRE_LANE_SUB_G2 = (2 + (F2S + F2M) + (F2S + F2M) + NBITS * G2_DBL[0] + NADD * G2_MADD[0]
+                    + (2 + F2M) + (F2S + 3 * F2M) + 2)
+# HBH_DEC_SPLIT (k_wire_split.hip): product rounds of the lane-quad group law
+G1Q_DBL_ROUNDS, G1Q_MADD_ROUNDS, G1Q_ADD_ROUNDS = 3, 5, 5     # g1quad.hpp
+G2Q_DBL_ROUNDS, G2Q_MADD_ROUNDS = 4, 6                        # g2quad.hpp
+LANE_PAIR_PRODUCT = 1.5
+WIRE_SPLIT_SUB_G1_ROUNDS = (1 + 2 + 1 + 2 * NBITS * G1Q_DBL_ROUNDS + NADD * (G1Q_MADD_ROUNDS + G1Q_ADD_ROUNDS)
+                            + 3)                              # ... P' in one round, the compare in three
+WIRE_SPLIT_SUB_G2_ROUNDS = 2 + 1 + NBITS * G2Q_DBL_ROUNDS + NADD * G2Q_MADD_ROUNDS + 4   # lane-pair rounds
+WIRE_SPLIT_SUB_G2_FP = 1 + 1 + 1                              # to Montgomery, C1 conj(x), the factor N(y)
+
+WIRE_DECODE_ROLES = {
+    # (group, form): critical path of each role, Fp-product times
+    ("g1", "lane"): {"root": WIRE_ROOT_G1, "subgroup": WIRE_LANE_SUB_G1},
+    ("g2", "lane"): {"root": WIRE_ROOT_G2, "subgroup": WIRE_LANE_SUB_G2},
+    ("g1", "split"): {"root": WIRE_ROOT_G1, "subgroup": WIRE_SPLIT_SUB_G1_ROUNDS},
+    ("g2", "split"): {"root": WIRE_ROOT_G2,
+                      "subgroup": WIRE_SPLIT_SUB_G2_ROUNDS * LANE_PAIR_PRODUCT + WIRE_SPLIT_SUB_G2_FP},
+}
+# products issued per point (every lane of a quad forms a product in every round)
+WIRE_DECODE_PRODUCTS = {
+    ("g1", "lane"): WIRE_ROOT_G1 + WIRE_LANE_SUB_G1,
+    ("g2", "lane"): WIRE_ROOT_G2 + WIRE_LANE_SUB_G2,
+    ("g1", "split"): WIRE_ROOT_G1 + 4 * WIRE_SPLIT_SUB_G1_ROUNDS,
+    ("g2", "split"): WIRE_ROOT_G2 + 4 * (WIRE_SPLIT_SUB_G2_ROUNDS * LANE_PAIR_PRODUCT + WIRE_SPLIT_SUB_G2_FP),
+}
+
+
+def wire_decode_critical_path(group, form):
+    """The longer role's chain: what a batch small enough to give every wave its own SIMD waits for."""
+    return max(WIRE_DECODE_ROLES[(group, form)].values())
+
+
+def wire_split_model_ratio(group):
+    """Predicted SPLIT / LANE time of a small batch (op model only: no issue rate, no memory)."""
+    return wire_decode_critical_path(group, "split") / wire_decode_critical_path(group, "lane")

@@ -251,6 +251,26 @@ int hbh_g1_decompress(hbh_engine* eng, size_t n, const uint8_t* in, uint8_t* out
  * the first byte; y^2 = x^3 + 4(1 + u); larger y by pairing 0.14's Fq2 order: c1, then c0);
  * out = ABI G2 points.  Same ok / all-zero convention as hbh_g1_decompress. */
 int hbh_g2_decompress(hbh_engine* eng, size_t n, const uint8_t* in, uint8_t* out, uint8_t* ok);
+/* Decoding kernels of hbh_g1_decompress, hbh_g2_decompress and their _dev forms (same bytes and ok
+ * verdicts from either):
+ *   HBH_DEC_LANE (k_wire.hip): 64 points per workgroup, one lane per point takes the square root
+ *     while one lane per point runs the whole subgroup chain -- throughput.
+ *   HBH_DEC_SPLIT (k_wire_split.hip): 16 points per workgroup, one lane per point takes the square
+ *     root while FOUR lanes per point split the group operations of the subgroup chain -- latency:
+ *     a small batch takes the time of the root chain instead of the (longer) subgroup chain.
+ *   HBH_DEC_AUTO (the default): SPLIT for n <= HBH_AUTO_DEC_G1_SPLIT_MAX / HBH_AUTO_DEC_G2_SPLIT_MAX
+ *     points per call (0: never), LANE above.  Thresholds: the largest swept size at which SPLIT's
+ *     median kernel time is below LANE's by more than both cells' min-max spread
+ *     (profiles/r07/decode_latency_sweep.json: wins at 4,096, loses at 16,384; refined in
+ *     profiles/r07/decode_latency_refine.json: 8,192 points are 512 workgroups = one wave on every
+ *     SIMD, and 8,208 start a second round; tools/decode_bench.py --impl both).
+ * A forced form runs for every n.  Any other value returns HBH_ERR_ARG and changes nothing. */
+#define HBH_DEC_AUTO 0
+#define HBH_DEC_LANE 1
+#define HBH_DEC_SPLIT 2
+#define HBH_AUTO_DEC_G1_SPLIT_MAX 8192
+#define HBH_AUTO_DEC_G2_SPLIT_MAX 8192
+int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
 
 /* ---------------------------------------------------------------- host stage (CPU, no engine)
  * What the north star keeps on the host, batched over `threads` std::thread workers (0 = all
