@@ -17,6 +17,10 @@
 #include "launch.hpp"
 #include "interp_pair.hpp"
 #include "wire.hpp"
+// host arithmetic and planning (no HIP, tested on the CPU: tests/test_engine_host.py)
+#include "host_fr.hpp"
+#include "wire_host.hpp"
+#include "ack_plan.hpp"
 
 namespace {
 
@@ -54,6 +58,19 @@ struct DevBuf {
     cap = 0;
   }
 };
+
+// Staging on a call's stream: upload grows the buffer first; h2d fills a part of a buffer that holds
+// several arrays.
+hipError_t h2d(hipStream_t s, void* dst, const void* src, size_t bytes) {
+  return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
+}
+hipError_t upload(hipStream_t s, DevBuf& b, const void* src, size_t bytes) {
+  const hipError_t err = b.ensure(bytes);
+  return err == hipSuccess ? h2d(s, b.p, src, bytes) : err;
+}
+hipError_t download(hipStream_t s, void* dst, const DevBuf& b, size_t bytes) {
+  return hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, s);
+}
 
 }  // namespace
 
@@ -152,19 +169,98 @@ void release_set_device(hbh_commit_set* cs);
 
 namespace {
 
-// Start of a call on stream s: order it after the engine's previous call.
-int begin_call(hbh_engine* e, hipStream_t s) {
-  HBH_CHECK(hipStreamWaitEvent(s, e->done, 0));
-  HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[0], 0));
-  HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[1], 0));
-  return HBH_OK;
-}
-int end_call(hbh_engine* e, hipStream_t s) {
-  HBH_CHECK(hipEventRecord(e->done, s));
-  HBH_CHECK(hipEventRecord(e->slot_done[0], s));
-  HBH_CHECK(hipEventRecord(e->slot_done[1], s));
-  return HBH_OK;
-}
+// One call on the engine, opened after the argument checks: holds the engine lock, makes the engine's
+// device current, picks the stream (a _dev call's `stream`, NULL = the engine stream) and orders the
+// call after the engine's earlier work.
+//   GENERAL    waits for done and both table slots; records all three on close
+//   PAIR_SLOT  takes the next table slot: waits for done and that slot's previous user; records the slot
+//   WIRE_SLOT  the same with the staging slots of device-pointer point decoding
+// finish() closes the call: it records the mode's events and, for a host-pointer call (sync), waits
+// for the stream -- after the downloads the call queued.  A call that returns without finish(), as
+// every failing one does, is closed the same way by the destructor, best effort: the next call on
+// another stream still waits for this call's queued kernels, and no queued copy outlives the caller's
+// buffers or the function's locals.
+struct EngineCall {
+  enum Mode { GENERAL, PAIR_SLOT, WIRE_SLOT };
+  hbh_engine* const e;
+  const bool sync;
+  const Mode mode;
+  std::lock_guard<std::mutex> lk;
+  hipStream_t s = nullptr;
+  int slot = 0;
+  int rc;  // HBH_OK: the call is open
+  bool closed = false;
+
+  EngineCall(hbh_engine* e, void* stream, bool sync, Mode mode = GENERAL) : e(e), sync(sync), mode(mode), lk(e->mu) {
+    rc = open(stream);
+    closed = rc != HBH_OK;
+  }
+  ~EngineCall() {
+    if (closed) return;
+    hipEvent_t ev[3];
+    for (int k = 0, n = events(ev); k < n; k++) (void)hipEventRecord(ev[k], s);
+    if (sync) (void)hipStreamSynchronize(s);
+  }
+  EngineCall(const EngineCall&) = delete;
+  EngineCall& operator=(const EngineCall&) = delete;
+
+  int finish() {
+    closed = true;
+    hipEvent_t ev[3];
+    hipError_t err = hipSuccess;
+    for (int k = 0, n = events(ev); k < n && err == hipSuccess; k++) err = hipEventRecord(ev[k], s);
+    if (err != hipSuccess) {
+      if (sync) (void)hipStreamSynchronize(s);
+      return fail(HBH_ERR_DEVICE, std::string("hipEventRecord: ") + hipGetErrorString(err));
+    }
+    if (sync) HBH_CHECK(hipStreamSynchronize(s));
+    return HBH_OK;
+  }
+
+ private:
+  int open(void* stream) {
+    HBH_CHECK(hipSetDevice(e->device));
+    s = stream ? (hipStream_t)stream : e->stream;
+    HBH_CHECK(hipStreamWaitEvent(s, e->done, 0));
+    if (mode == GENERAL) {
+      HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[0], 0));
+      HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[1], 0));
+    } else if (mode == PAIR_SLOT) {
+      slot = e->slot;
+      e->slot ^= 1;
+      HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[slot], 0));
+    } else {
+      slot = e->wire_slot;
+      e->wire_slot ^= 1;
+      HBH_CHECK(hipStreamWaitEvent(s, e->wire_done[slot], 0));
+    }
+    return HBH_OK;
+  }
+  int events(hipEvent_t ev[3]) const {
+    if (mode == PAIR_SLOT) return ev[0] = e->slot_done[slot], 1;
+    if (mode == WIRE_SLOT) return ev[0] = e->wire_done[slot], 1;
+    ev[0] = e->done;
+    ev[1] = e->slot_done[0];
+    ev[2] = e->slot_done[1];
+    return 3;
+  }
+};
+
+// A timed stage on stream s: the begin event now, the end event at stop() or on leaving the scope,
+// so every exit records it (hbh_engine_stage_time reads both events of every pair).
+struct StageScope {
+  hbh_engine* const e;
+  const hipStream_t s;
+  hipEvent_t b;
+  StageScope(hbh_engine* e, hipStream_t s, int stage) : e(e), s(s), b(e->timer.begin(s, stage, e->profiling)) {}
+  ~StageScope() { stop(); }
+  StageScope(const StageScope&) = delete;
+  StageScope& operator=(const StageScope&) = delete;
+  void stop() {
+    e->timer.end(s, b);
+    b = nullptr;
+  }
+};
 
 int resolve_impl(const hbh_engine* e, size_t n) {
   if (e->impl != HBH_IMPL_AUTO) return e->impl;
@@ -198,6 +294,16 @@ hipError_t wave2_verify(hipStream_t s, int n, const hbl::PairSideDesc& a, const 
   return hbl::wave64_verify(s, n, a, b, flags, v, val);
 }
 
+// the pairing kernel of one implementation kind (not AUTO: verify_auto splits a call among these)
+hipError_t verify_kind(int kind, hipStream_t s, int n, const hbl::PairSideDesc& a, const hbl::PairSideDesc& b,
+                       int flags, uint8_t* v, uint32_t* val) {
+  if (kind == HBH_IMPL_WAVE2) return wave2_verify(s, n, a, b, flags, v, val);
+  if (kind == HBH_IMPL_WAVE) return hbl::wave_verify(s, n, a, b, flags, v, val);
+  if (kind == HBH_IMPL_QUAD) return hbl::quad_verify(s, n, a, b, flags, v, val);
+  if (kind == HBH_IMPL_OCT) return hbl::oct_verify(s, n, a, b, flags, v, val);
+  return hbl::pair_verify(s, n, a, b, flags, v, val);
+}
+
 // HBH_IMPL_AUTO's launches for n checks on one stream (profiles/r04/c8, c19, c20 sweeps): whole
 // rounds of HBH_AUTO_PAIR_ROUND checks (two lane-pair waves per SIMD) on PAIR, then the remainder by
 // size -- above HBH_AUTO_SPLIT_HI one more (partial) PAIR round; above HBH_AUTO_SPLIT_LO PAIR on
@@ -213,11 +319,7 @@ hipError_t verify_auto(hipStream_t s, size_t n, const hbl::PairSideDesc& s1, con
     const hbl::PairSideDesc a = o ? offset_side(s1, o) : s1, b = o ? offset_side(s2, o) : s2;
     uint8_t* v = d_v ? d_v + o : nullptr;
     uint32_t* val = d_value ? d_value + o * 144 : nullptr;
-    if (kind == HBH_IMPL_WAVE2) return wave2_verify(s, (int)cnt, a, b, flags, v, val);
-    if (kind == HBH_IMPL_WAVE) return hbl::wave_verify(s, (int)cnt, a, b, flags, v, val);
-    if (kind == HBH_IMPL_QUAD) return hbl::quad_verify(s, (int)cnt, a, b, flags, v, val);
-    if (kind == HBH_IMPL_OCT) return hbl::oct_verify(s, (int)cnt, a, b, flags, v, val);
-    return hbl::pair_verify(s, (int)cnt, a, b, flags, v, val);
+    return verify_kind(kind, s, (int)cnt, a, b, flags, v, val);
   };
   if (n > HBH_AUTO_SPLIT_HI) {  // whole two-wave lane-pair rounds
     off = (n / HBH_AUTO_PAIR_ROUND) * HBH_AUTO_PAIR_ROUND;
@@ -260,26 +362,16 @@ int launch_pair(hbh_engine* e, hipStream_t s, int impl, size_t n, const void* d_
     if (impl == HBH_IMPL_WAVE && !(tab_ok[0] && tab_ok[1] && n >= HBH_WAVE_TT_MIN)) continue;
     HBH_CHECK(tab[k]->ensure(hbl::pair_table_bytes(sd[k].nq)));
     HBH_CHECK(inf[k]->ensure(sd[k].nq));
-    hipEvent_t t = e->timer.begin(s, HBH_STAGE_PREPARE, e->profiling);
+    StageScope tm(e, s, HBH_STAGE_PREPARE);
     HBH_CHECK(hbl::oct_prep(s, (int)sd[k].nq, sd[k].q, tab[k]->p, (uint8_t*)inf[k]->p));
-    e->timer.end(s, t);
     sd[k].lines = tab[k]->p;
     sd[k].qinf = (const uint8_t*)inf[k]->p;
   }
-  hipEvent_t t = e->timer.begin(s, HBH_STAGE_PAIRING, e->profiling);
+  StageScope tm(e, s, HBH_STAGE_PAIRING);
   if (e->impl == HBH_IMPL_AUTO)
     HBH_CHECK(verify_auto(s, n, sd[0], sd[1], flags, d_v, d_value));
-  else if (impl == HBH_IMPL_WAVE)
-    HBH_CHECK(hbl::wave_verify(s, (int)n, sd[0], sd[1], flags, d_v, d_value));
-  else if (impl == HBH_IMPL_WAVE2)
-    HBH_CHECK(wave2_verify(s, (int)n, sd[0], sd[1], flags, d_v, d_value));
-  else if (impl == HBH_IMPL_QUAD)
-    HBH_CHECK(hbl::quad_verify(s, (int)n, sd[0], sd[1], flags, d_v, d_value));
-  else if (impl == HBH_IMPL_OCT)
-    HBH_CHECK(hbl::oct_verify(s, (int)n, sd[0], sd[1], flags, d_v, d_value));
   else
-    HBH_CHECK(hbl::pair_verify(s, (int)n, sd[0], sd[1], flags, d_v, d_value));
-  e->timer.end(s, t);
+    HBH_CHECK(verify_kind(impl, s, (int)n, sd[0], sd[1], flags, d_v, d_value));
   return HBH_OK;
 }
 
@@ -311,38 +403,22 @@ int run_pairing_eq_host(hbh_engine* e, size_t n, const uint8_t* p1, const uint8_
   if (rc) return rc;
   rc = check_idx(i2, n, nq2);
   if (rc) return rc;
-  hipStream_t s = e->stream;
-  rc = begin_call(e, s);
-  if (rc) return rc;
-  if (p1) HBH_CHECK(e->in_p1.ensure(n * HBH_G1_BYTES));
-  if (p2) HBH_CHECK(e->in_p2.ensure(n * HBH_G1_BYTES));
-  HBH_CHECK(e->in_q1.ensure(nq1 * HBH_G2_BYTES));
-  HBH_CHECK(e->in_q2.ensure(nq2 * HBH_G2_BYTES));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  if (p1) HBH_CHECK(upload(s, e->in_p1, p1, n * HBH_G1_BYTES));
+  if (p2) HBH_CHECK(upload(s, e->in_p2, p2, n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_q1, q1, nq1 * HBH_G2_BYTES));
+  HBH_CHECK(upload(s, e->in_q2, q2, nq2 * HBH_G2_BYTES));
   HBH_CHECK(e->out_v.ensure(n));
-  if (p1) HBH_CHECK(hipMemcpyAsync(e->in_p1.p, p1, n * HBH_G1_BYTES, hipMemcpyHostToDevice, s));
-  if (p2) HBH_CHECK(hipMemcpyAsync(e->in_p2.p, p2, n * HBH_G1_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_q1.p, q1, nq1 * HBH_G2_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_q2.p, q2, nq2 * HBH_G2_BYTES, hipMemcpyHostToDevice, s));
-  const uint32_t* d_i1 = nullptr;
-  const uint32_t* d_i2 = nullptr;
-  if (i1) {
-    HBH_CHECK(e->in_i1.ensure(n * 4));
-    HBH_CHECK(hipMemcpyAsync(e->in_i1.p, i1, n * 4, hipMemcpyHostToDevice, s));
-    d_i1 = (const uint32_t*)e->in_i1.p;
-  }
-  if (i2) {
-    HBH_CHECK(e->in_i2.ensure(n * 4));
-    HBH_CHECK(hipMemcpyAsync(e->in_i2.p, i2, n * 4, hipMemcpyHostToDevice, s));
-    d_i2 = (const uint32_t*)e->in_i2.p;
-  }
-  rc = run_pairing_dev(e, s, n, p1 ? e->in_p1.p : nullptr, e->in_q1.p, nq1, d_i1, p2 ? e->in_p2.p : nullptr,
-                       e->in_q2.p, nq2, d_i2, 1, (uint8_t*)e->out_v.p);
+  if (i1) HBH_CHECK(upload(s, e->in_i1, i1, n * 4));
+  if (i2) HBH_CHECK(upload(s, e->in_i2, i2, n * 4));
+  rc = run_pairing_dev(e, s, n, p1 ? e->in_p1.p : nullptr, e->in_q1.p, nq1, i1 ? (const uint32_t*)e->in_i1.p : nullptr,
+                       p2 ? e->in_p2.p : nullptr, e->in_q2.p, nq2, i2 ? (const uint32_t*)e->in_i2.p : nullptr, 1,
+                       (uint8_t*)e->out_v.p);
   if (rc) return rc;
-  HBH_CHECK(hipMemcpyAsync(v, e->out_v.p, n, hipMemcpyDeviceToHost, s));
-  rc = end_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, v, e->out_v, n));
+  return call.finish();
 }
 
 }  // namespace
@@ -442,8 +518,6 @@ int hbh_verify_pairing_eq(hbh_engine* e, size_t n, const uint8_t* p1, const uint
                           uint8_t* v) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n && (!p1 || !p2)) return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
   return run_pairing_eq_host(e, n, p1, q1, nq1, i1, p2, q2, nq2, i2, v);
 }
 
@@ -453,19 +527,13 @@ int hbh_verify_pairing_eq_dev(hbh_engine* e, void* stream, size_t n, const void*
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n && (!d_q1 || !d_q2 || !d_v)) return fail(HBH_ERR_ARG, "null pointer");
   if ((!d_i1 && nq1 != n) || (!d_i2 && nq2 != n)) return fail(HBH_ERR_ARG, "identity index map requires table size == n");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = stream ? (hipStream_t)stream : e->stream;
   if (n == 0) return HBH_OK;
   // table slot of its own: wait for the last general call and for this slot's previous user only
-  const int slot = e->slot;
-  e->slot ^= 1;
-  HBH_CHECK(hipStreamWaitEvent(s, e->done, 0));
-  HBH_CHECK(hipStreamWaitEvent(s, e->slot_done[slot], 0));
-  int rc = run_pairing_dev(e, s, n, d_p1, d_q1, nq1, d_i1, d_p2, d_q2, nq2, d_i2, 1, d_v, nullptr, slot);
+  EngineCall call(e, stream, false, EngineCall::PAIR_SLOT);
+  if (call.rc) return call.rc;
+  int rc = run_pairing_dev(e, call.s, n, d_p1, d_q1, nq1, d_i1, d_p2, d_q2, nq2, d_i2, 1, d_v, nullptr, call.slot);
   if (rc) return rc;
-  HBH_CHECK(hipEventRecord(e->slot_done[slot], s));
-  return HBH_OK;
+  return call.finish();
 }
 
 int hbh_verify_sig_shares(hbh_engine* e, size_t n, const uint8_t* pks, const uint8_t* sigs, const uint8_t* hashes,
@@ -473,8 +541,6 @@ int hbh_verify_sig_shares(hbh_engine* e, size_t n, const uint8_t* pks, const uin
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n == 0) return HBH_OK;
   if (!pks || !sigs) return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
   return run_pairing_eq_host(e, n, pks, hashes, ndocs, doc_idx, nullptr, sigs, n, nullptr, v);
 }
 
@@ -482,8 +548,6 @@ int hbh_verify_dec_shares(hbh_engine* e, size_t n, const uint8_t* shares, const 
                           const uint8_t* w, size_t ncts, const uint32_t* ct_idx, uint8_t* v) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n && (!shares || !pks)) return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
   return run_pairing_eq_host(e, n, shares, huv, ncts, ct_idx, pks, w, ncts, ct_idx, v);
 }
 
@@ -492,8 +556,6 @@ int hbh_verify_ciphertexts(hbh_engine* e, size_t n, const uint8_t* u, const uint
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n == 0) return HBH_OK;
   if (!u) return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
   return run_pairing_eq_host(e, n, nullptr, w, n, nullptr, u, huv, n, nullptr, v);
 }
 
@@ -501,26 +563,19 @@ int hbh_dbg_pairing(hbh_engine* e, size_t n, const uint8_t* p, const uint8_t* q,
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n == 0) return HBH_OK;
   if (!p || !q || !out) return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  int rc = begin_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(e->in_p1.ensure(n * HBH_G1_BYTES));
-  HBH_CHECK(e->in_q1.ensure(n * HBH_G2_BYTES));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_p1, p, n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_q1, q, n * HBH_G2_BYTES));
   HBH_CHECK(e->out_v.ensure(n * 576));
-  HBH_CHECK(hipMemcpyAsync(e->in_p1.p, p, n * HBH_G1_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_q1.p, q, n * HBH_G2_BYTES, hipMemcpyHostToDevice, s));
   HBH_CHECK(e->in_p2.ensure(n * HBH_G1_BYTES));
   HBH_CHECK(hipMemsetAsync(e->in_p2.p, 0, n * HBH_G1_BYTES, s));  // second pair inactive (P2 = O)
-  rc = run_pairing_dev(e, s, n, e->in_p1.p, e->in_q1.p, n, nullptr, e->in_p2.p, e->in_q1.p, n, nullptr, 2, nullptr,
-                       (uint32_t*)e->out_v.p);
+  int rc = run_pairing_dev(e, s, n, e->in_p1.p, e->in_q1.p, n, nullptr, e->in_p2.p, e->in_q1.p, n, nullptr, 2, nullptr,
+                           (uint32_t*)e->out_v.p);
   if (rc) return rc;
-  HBH_CHECK(hipMemcpyAsync(out, e->out_v.p, n * 576, hipMemcpyDeviceToHost, s));
-  rc = end_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_v, n * 576));
+  return call.finish();
 }
 
 int hbh_engine_set_pairing_impl(hbh_engine* e, int impl) {
@@ -590,28 +645,18 @@ int run_mul(hbh_engine* e, size_t n, const uint8_t* pts, size_t pt_bytes, const 
   if (n == 0) return HBH_OK;
   if (!pts || !scalars || !out) return fail(HBH_ERR_ARG, "null pointer");
   if (n > (size_t)1 << 28) return fail(HBH_ERR_ARG, "batch too large");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(e->in_a.ensure(n * pt_bytes));
-  HBH_CHECK(e->in_b.ensure(n * HBH_FR_BYTES));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, pts, n * pt_bytes));
+  HBH_CHECK(upload(s, e->in_b, scalars, n * HBH_FR_BYTES));
   HBH_CHECK(e->out_x.ensure(n * pt_bytes));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, pts, n * pt_bytes, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, scalars, n * HBH_FR_BYTES, hipMemcpyHostToDevice, s));
-  hipEvent_t t = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(launch(s, (int)n, e->in_a.p, (const uint32_t*)e->in_b.p, e->out_x.p));
-  e->timer.end(s, t);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, n * pt_bytes, hipMemcpyDeviceToHost, s));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(launch(s, (int)n, e->in_a.p, (const uint32_t*)e->in_b.p, e->out_x.p));
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, n * pt_bytes));
+  return call.finish();
 }
 
 // The g1 comb table, built on the engine stream the first time a call needs it.
@@ -636,205 +681,6 @@ int ensure_fb16(hbh_engine* e, hipStream_t s) {
   return HBH_OK;
 }
 
-// ---- host Fr (4 x 64-bit Montgomery, R = 2^256) for the Lagrange digits of one or two combines:
-// on the host they cost tens of microseconds, less than a kernel launch of k_interp_digits.
-struct HFr {
-  uint64_t l[4];
-};
-constexpr uint64_t HFR_P[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull,
-                               0x73eda753299d7d48ull};
-constexpr uint64_t HFR_NP = 0xfffffffeffffffffull;  // -r^-1 mod 2^64
-constexpr uint64_t HFR_R2[4] = {0xc999e990f3f29c6dull, 0x2b6cedcb87925c23ull, 0x05d314967254398full,
-                                0x0748d9d99f59ff11ull};
-using u128 = unsigned __int128;
-
-bool hfr_geq_p(const uint64_t* a) {
-  for (int i = 3; i >= 0; i--)
-    if (a[i] != HFR_P[i]) return a[i] > HFR_P[i];
-  return true;
-}
-void hfr_sub_p(uint64_t* a) {
-  u128 br = 0;
-  for (int i = 0; i < 4; i++) {
-    const u128 d = (u128)a[i] - HFR_P[i] - br;
-    a[i] = (uint64_t)d;
-    br = (d >> 64) ? 1 : 0;
-  }
-}
-HFr hfr_mul(const HFr& a, const HFr& b) {  // CIOS
-  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < 4; i++) {
-    u128 c = 0;
-    for (int j = 0; j < 4; j++) {
-      c += (u128)a.l[j] * b.l[i] + t[j];
-      t[j] = (uint64_t)c;
-      c >>= 64;
-    }
-    c += t[4];
-    t[4] = (uint64_t)c;
-    t[5] = (uint64_t)(c >> 64);
-    const uint64_t m = t[0] * HFR_NP;
-    c = (u128)m * HFR_P[0] + t[0];
-    c >>= 64;
-    for (int j = 1; j < 4; j++) {
-      c += (u128)m * HFR_P[j] + t[j];
-      t[j - 1] = (uint64_t)c;
-      c >>= 64;
-    }
-    c += t[4];
-    t[3] = (uint64_t)c;
-    t[4] = t[5] + (uint64_t)(c >> 64);
-  }
-  HFr r{{t[0], t[1], t[2], t[3]}};
-  if (t[4] || hfr_geq_p(r.l)) hfr_sub_p(r.l);
-  return r;
-}
-HFr hfr_from_u64(uint64_t v) { return hfr_mul(HFr{{v, 0, 0, 0}}, HFr{{HFR_R2[0], HFR_R2[1], HFR_R2[2], HFR_R2[3]}}); }
-HFr hfr_sub(const HFr& a, const HFr& b) {
-  HFr r;
-  u128 br = 0;
-  for (int i = 0; i < 4; i++) {
-    const u128 d = (u128)a.l[i] - b.l[i] - br;
-    r.l[i] = (uint64_t)d;
-    br = (d >> 64) ? 1 : 0;
-  }
-  if (br) {
-    u128 c = 0;
-    for (int i = 0; i < 4; i++) {
-      c += (u128)r.l[i] + HFR_P[i];
-      r.l[i] = (uint64_t)c;
-      c >>= 64;
-    }
-  }
-  return r;
-}
-bool hfr_is_zero(const HFr& a) { return !(a.l[0] | a.l[1] | a.l[2] | a.l[3]); }
-HFr hfr_inv(const HFr& a) {  // a^(r-2)
-  uint64_t e[4] = {HFR_P[0] - 2, HFR_P[1], HFR_P[2], HFR_P[3]};
-  HFr r = hfr_from_u64(1);
-  for (int i = 255; i >= 0; i--) {
-    r = hfr_mul(r, r);
-    if ((e[i >> 6] >> (i & 63)) & 1) r = hfr_mul(r, a);
-  }
-  return r;
-}
-void hfr_to_canon(const HFr& a, uint64_t* out) {
-  const HFr c = hfr_mul(a, HFr{{1, 0, 0, 0}});
-  for (int i = 0; i < 4; i++) out[i] = c.l[i];
-}
-
-// k_interp_digits on the host: the four GLS digits (base |x|) of every lambda_k(0) of each combine;
-// status[c] = HBH_ERR_DUPLICATE_ENTRY and zero digits on a repeated x
-// q (4 x u64) <- q / x^2, rem <- q mod x^2 (bit-serial, the host twin of k_curve.hip div_x2)
-void host_div_x2(uint64_t q[4], uint64_t rem[2]) {
-  constexpr uint64_t X2_LO = 0x0000000100000000ull, X2_HI = 0xac45a4010001a402ull;
-  uint64_t r0 = 0, r1 = 0;
-  for (int w = 3; w >= 0; w--) {
-    uint64_t qw = 0;
-    for (int b = 63; b >= 0; b--) {
-      const bool top = (r1 >> 63) != 0;
-      r1 = (r1 << 1) | (r0 >> 63);
-      r0 = (r0 << 1) | ((q[w] >> b) & 1);
-      const bool ge = top || r1 > X2_HI || (r1 == X2_HI && r0 >= X2_LO);
-      if (ge) {
-        const uint64_t nr0 = r0 - X2_LO;
-        r1 = r1 - X2_HI - (r0 < X2_LO ? 1 : 0);
-        r0 = nr0;
-      }
-      qw |= (uint64_t)ge << b;
-    }
-    q[w] = qw;
-  }
-  rem[0] = r0;
-  rem[1] = r1;
-}
-
-// lambda_k(0) = prod_{j != k} x_j / (x_j - x_k) of every sample of each combine, canonical (4 x u64
-// LE per sample); status[c] = HBH_ERR_DUPLICATE_ENTRY and zero lambdas on a repeated x
-void host_lagrange(const uint32_t* xs, size_t ncomb, size_t m, uint64_t* lam, int* status) {
-  std::vector<HFr> x(m), num(m), den(m), pre(m);
-  for (size_t c = 0; c < ncomb; c++) {
-    const uint32_t* cx = xs + c * m;
-    for (size_t k = 0; k < m; k++) x[k] = hfr_from_u64(cx[k]);
-    bool dup = false;
-    for (size_t k = 0; k < m; k++) {
-      HFr n = hfr_from_u64(1), d = hfr_from_u64(1);
-      for (size_t j = 0; j < m; j++) {
-        if (j == k) continue;
-        n = hfr_mul(n, x[j]);
-        d = hfr_mul(d, hfr_sub(x[j], x[k]));
-      }
-      dup = dup || hfr_is_zero(d);
-      num[k] = n;
-      den[k] = d;
-    }
-    status[c] = dup ? HBH_ERR_DUPLICATE_ENTRY : HBH_OK;
-    uint64_t* lc = lam + c * m * 4;
-    if (dup) {
-      std::memset(lc, 0, m * 4 * sizeof(uint64_t));
-      continue;
-    }
-    pre[0] = den[0];
-    for (size_t k = 1; k < m; k++) pre[k] = hfr_mul(pre[k - 1], den[k]);
-    HFr inv = hfr_inv(pre[m - 1]);
-    for (size_t k = m; k-- > 0;) {
-      const HFr ik = k ? hfr_mul(inv, pre[k - 1]) : inv;
-      if (k) inv = hfr_mul(inv, den[k]);
-      hfr_to_canon(hfr_mul(num[k], ik), lc + k * 4);
-    }
-  }
-}
-
-// the four GLS digits (base |x|) of n canonical scalars (4 x u64 each): q <- q / |x| three times, digit j
-// = remainder, digit 3 = the last quotient
-void host_gls_digits(const uint64_t* lam, size_t n, uint64_t* dg) {
-  constexpr uint64_t XA = 0xd201000000010000ull;
-  for (size_t k = 0; k < n; k++) {
-    uint64_t q[4] = {lam[k * 4], lam[k * 4 + 1], lam[k * 4 + 2], lam[k * 4 + 3]};
-    for (int j = 0; j < 3; j++) {
-      u128 rem = 0;
-      for (int w = 3; w >= 0; w--) {
-        const u128 cur = (rem << 64) | q[w];
-        q[w] = (uint64_t)(cur / XA);
-        rem = cur % XA;
-      }
-      dg[k * 4 + j] = (uint64_t)rem;
-    }
-    dg[k * 4 + 3] = q[0];
-  }
-}
-
-void host_interp_digits(const uint32_t* xs, size_t ncomb, size_t m, uint64_t* digits, int* status, bool g1 = false) {
-  constexpr uint64_t XA = 0xd201000000010000ull;
-  host_lagrange(xs, ncomb, m, digits, status);  // in place: lambda_k's 4 words become its 4 digits
-  for (size_t c = 0; c < ncomb; c++) {
-    uint64_t* dg = digits + c * m * 4;
-    if (status[c] != HBH_OK) continue;
-    for (size_t k = 0; k < m; k++) {
-      uint64_t q[4] = {dg[k * 4], dg[k * 4 + 1], dg[k * 4 + 2], dg[k * 4 + 3]};
-      if (g1) {  // lambda = d0 + d1 x^2
-        uint64_t rem[2];
-        host_div_x2(q, rem);
-        dg[k * 4 + 0] = rem[0];
-        dg[k * 4 + 1] = rem[1];
-        dg[k * 4 + 2] = q[0];
-        dg[k * 4 + 3] = q[1];
-        continue;
-      }
-      for (int j = 0; j < 3; j++) {  // q <- q / |x|, digit j = remainder
-        u128 rem = 0;
-        for (int w = 3; w >= 0; w--) {
-          const u128 cur = (rem << 64) | q[w];
-          q[w] = (uint64_t)(cur / XA);
-          rem = cur % XA;
-        }
-        dg[k * 4 + j] = (uint64_t)rem;
-      }
-      dg[k * 4 + 3] = q[0];
-    }
-  }
-}
-
 // G2 combines: few combines (latency-bound: the chip is idle but for the serial chains) take the
 // lane-pair form (digits + k_interp_pair); many take k_interp_endo (throughput form).  With the x
 // values on the host and at most HOST_DIGITS_MAX combines, the digits are computed on the host and
@@ -844,19 +690,28 @@ void host_interp_digits(const uint32_t* xs, size_t ncomb, size_t m, uint64_t* di
 #endif
 constexpr size_t INTERP_PAIR_MAX = HBH_INTERP_PAIR_MAX;
 constexpr size_t HOST_DIGITS_MAX = 2;
+// The digits of a combine call in e->in_d (four base-|x| digits per sample, g1: two base-x^2 digits):
+// from the host when the x values are there and the call is small, else by k_interp_digits.
+int stage_digits(hbh_engine* e, hipStream_t s, size_t ncomb, size_t m, const uint32_t* d_xs, int* d_status,
+                 const uint32_t* h_xs, bool g1) {
+  HBH_CHECK(e->in_d.ensure(ncomb * m * 4 * sizeof(uint64_t)));
+  if (h_xs && ncomb <= HOST_DIGITS_MAX) {
+    e->h_digits.resize(ncomb * m * 4);
+    e->h_status.resize(ncomb);
+    host_interp_digits(h_xs, ncomb, m, e->h_digits.data(), e->h_status.data(), g1);
+    HBH_CHECK(h2d(s, e->in_d.p, e->h_digits.data(), ncomb * m * 32));
+    HBH_CHECK(h2d(s, d_status, e->h_status.data(), ncomb * sizeof(int)));
+  } else {
+    HBH_CHECK(hbl::interp_digits(s, (int)ncomb, (int)m, d_xs, (uint64_t*)e->in_d.p, d_status, g1));
+  }
+  return HBH_OK;
+}
+
 int launch_combine_g2(hbh_engine* e, hipStream_t s, size_t ncomb, size_t m, const uint32_t* d_xs, const void* d_pts,
                       void* d_out, int* d_status, const uint32_t* h_xs = nullptr) {
   if (ncomb <= INTERP_PAIR_MAX && hbl::interp_g2_pair_fits((int)m)) {
-    HBH_CHECK(e->in_d.ensure(ncomb * m * 4 * sizeof(uint64_t)));
-    if (h_xs && ncomb <= HOST_DIGITS_MAX) {
-      e->h_digits.resize(ncomb * m * 4);
-      e->h_status.resize(ncomb);
-      host_interp_digits(h_xs, ncomb, m, e->h_digits.data(), e->h_status.data());
-      HBH_CHECK(hipMemcpyAsync(e->in_d.p, e->h_digits.data(), ncomb * m * 32, hipMemcpyHostToDevice, s));
-      HBH_CHECK(hipMemcpyAsync(d_status, e->h_status.data(), ncomb * sizeof(int), hipMemcpyHostToDevice, s));
-    } else {
-      HBH_CHECK(hbl::interp_digits(s, (int)ncomb, (int)m, d_xs, (uint64_t*)e->in_d.p, d_status));
-    }
+    const int rc = stage_digits(e, s, ncomb, m, d_xs, d_status, h_xs, false);
+    if (rc) return rc;
     HBH_CHECK(e->ipart.ensure(hbl::interp_g2_pair_part_bytes((int)ncomb)));
     HBH_CHECK(hbl::interp_g2_pair(s, (int)ncomb, (int)m, (const uint64_t*)e->in_d.p, d_pts, e->ipart.p, d_out));
     return HBH_OK;
@@ -873,22 +728,19 @@ int launch_combine_g2(hbh_engine* e, hipStream_t s, size_t ncomb, size_t m, cons
 int launch_combine_g1(hbh_engine* e, hipStream_t s, size_t ncomb, size_t m, const uint32_t* d_xs, const void* d_pts,
                       void* d_out, int* d_status, const uint32_t* h_xs = nullptr) {
   if (ncomb <= HBH_INTERP_G1Q_MAX && m <= 4096) {
-    HBH_CHECK(e->in_d.ensure(ncomb * m * 4 * sizeof(uint64_t)));
-    if (h_xs && ncomb <= HOST_DIGITS_MAX) {
-      e->h_digits.resize(ncomb * m * 4);
-      e->h_status.resize(ncomb);
-      host_interp_digits(h_xs, ncomb, m, e->h_digits.data(), e->h_status.data(), true);
-      HBH_CHECK(hipMemcpyAsync(e->in_d.p, e->h_digits.data(), ncomb * m * 32, hipMemcpyHostToDevice, s));
-      HBH_CHECK(hipMemcpyAsync(d_status, e->h_status.data(), ncomb * sizeof(int), hipMemcpyHostToDevice, s));
-    } else {
-      HBH_CHECK(hbl::interp_digits(s, (int)ncomb, (int)m, d_xs, (uint64_t*)e->in_d.p, d_status, true));
-    }
+    const int rc = stage_digits(e, s, ncomb, m, d_xs, d_status, h_xs, true);
+    if (rc) return rc;
     HBH_CHECK(e->ipart.ensure(hbl::interp_g1_quad_part_bytes((int)ncomb)));
     HBH_CHECK(hbl::interp_g1_quad(s, (int)ncomb, (int)m, (const uint64_t*)e->in_d.p, d_pts, e->ipart.p, d_out));
     return HBH_OK;
   }
   HBH_CHECK(hbl::combine_g1(s, (int)ncomb, (int)m, d_xs, d_pts, d_out, d_status));
   return HBH_OK;
+}
+int launch_combine(hbh_engine* e, hipStream_t s, bool g2, size_t ncomb, size_t m, const uint32_t* d_xs,
+                   const void* d_pts, void* d_out, int* d_status, const uint32_t* h_xs = nullptr) {
+  return g2 ? launch_combine_g2(e, s, ncomb, m, d_xs, d_pts, d_out, d_status, h_xs)
+            : launch_combine_g1(e, s, ncomb, m, d_xs, d_pts, d_out, d_status, h_xs);
 }
 
 int run_interp(hbh_engine* e, size_t ncomb, int t, const uint32_t* idx, const uint8_t* pts, uint8_t* out, int* status,
@@ -906,39 +758,23 @@ int run_interp(hbh_engine* e, size_t ncomb, int t, const uint32_t* idx, const ui
     if (idx[k] == 0xffffffffu) return fail(HBH_ERR_ARG, "node index out of range");
     xs[k] = idx[k] + 1;
   }
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(e->in_a.ensure(ncomb * m * 4));
-  HBH_CHECK(e->in_b.ensure(ncomb * m * pb));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, xs.data(), ncomb * m * 4));
+  HBH_CHECK(upload(s, e->in_b, pts, ncomb * m * pb));
   HBH_CHECK(e->out_x.ensure(ncomb * pb));
   HBH_CHECK(e->status.ensure(ncomb * sizeof(int)));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, xs.data(), ncomb * m * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, pts, ncomb * m * pb, hipMemcpyHostToDevice, s));
   HBH_CHECK(hipMemsetAsync(e->status.p, 0, ncomb * sizeof(int), s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  if (g2) {
-    rc = launch_combine_g2(e, s, ncomb, m, (const uint32_t*)e->in_a.p, e->in_b.p, e->out_x.p, (int*)e->status.p,
-                           xs.data());
-    if (rc) return rc;
-  } else {
-    rc = launch_combine_g1(e, s, ncomb, m, (const uint32_t*)e->in_a.p, e->in_b.p, e->out_x.p, (int*)e->status.p,
-                           xs.data());
-    if (rc) return rc;
-  }
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, ncomb * pb, hipMemcpyDeviceToHost, s));
-  HBH_CHECK(hipMemcpyAsync(status, e->status.p, ncomb * sizeof(int), hipMemcpyDeviceToHost, s));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    rc = launch_combine(e, s, g2, ncomb, m, (const uint32_t*)e->in_a.p, e->in_b.p, e->out_x.p, (int*)e->status.p,
+                        xs.data());
+    if (rc) return rc;
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, ncomb * pb));
+  HBH_CHECK(download(s, status, e->status, ncomb * sizeof(int)));
+  return call.finish();
 }
 
 // ThresholdSign::combine_and_verify_sig's master check split off the interpolation (few combines, the
@@ -978,8 +814,8 @@ int combine_verify_split(hbh_engine* e, size_t ncomb, size_t m, const std::vecto
                o_p1 = o_p0 + nchk * JB, o_i0 = o_p1 + nchk * JB, o_i1 = o_i0 + nchk * 4, in_bytes = o_i1 + nchk * 4;
   // one download: signatures | verdicts
   const size_t o_v = ncomb * HBH_G2_BYTES, out_bytes = o_v + ncomb;
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
   if (!e->side) {
     HBH_CHECK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     HBH_CHECK(hipEventCreateWithFlags(&e->fork, hipEventDisableTiming));
@@ -1018,22 +854,18 @@ int combine_verify_split(hbh_engine* e, size_t ncomb, size_t m, const std::vecto
           *qi = (uint32_t)(ncomb * m + c);  // then an inactive pad (P = O)
         }
       }
-  hipStream_t s = e->stream, s2 = e->side;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
+  hipStream_t s = call.s, s2 = e->side;
   HBH_CHECK(e->split_in.ensure(in_bytes));
   HBH_CHECK(e->split_out.ensure(out_bytes));
   HBH_CHECK(e->fval.ensure(nchk * 144 * 4));
   HBH_CHECK(e->ipart.ensure(hbl::interp_g2_pair_part_bytes((int)ncomb)));
   uint8_t* din = (uint8_t*)e->split_in.p;
   uint8_t* dout = (uint8_t*)e->split_out.p;
-  HBH_CHECK(hipMemcpyAsync(din, hs, in_bytes, hipMemcpyHostToDevice, s));
+  HBH_CHECK(h2d(s, din, hs, in_bytes));
   HBH_CHECK(hipEventRecord(e->fork, s));
   HBH_CHECK(hipStreamWaitEvent(s2, e->fork, 0));
-  // From here on both streams hold queued work: every exit joins the side stream into s and closes the
-  // call on s, so e->done covers the side stream's kernels even when a launch fails.
+  // From here on both streams hold queued work: every exit joins the side stream into s before the
+  // call closes on s, so e->done covers the side stream's kernels even when a launch fails.
   auto launch = [&]() -> int {
     // side stream: lambda_k g1 (Jacobian, over the zero P entries), the m + 1 Miller loops, the product
     // and the final exponentiation
@@ -1043,7 +875,7 @@ int combine_verify_split(hbh_engine* e, size_t ncomb, size_t m, const std::vecto
                                (const uint32_t*)(din + o_lam), din + o_p0, din + o_p1));
     hbl::PairSideDesc sd0 = {din + o_p0, din + o_q, nullptr, nullptr, (const uint32_t*)(din + o_i0), nq};
     hbl::PairSideDesc sd1 = {din + o_p1, din + o_q, nullptr, nullptr, (const uint32_t*)(din + o_i1), nq};
-    hipEvent_t tp = e->timer.begin(s2, HBH_STAGE_PAIRING, e->profiling);
+    StageScope tp(e, s2, HBH_STAGE_PAIRING);
     const int wflags = hbl::WAVE_MILLER_ONLY | hbl::WAVE_JAC_P | (pairs == 1 ? hbl::WAVE_ONE_SIDE : 0);
     if (e->split_tree) {  // product up a tree and the final exponentiation inside the Miller launch
       HBH_CHECK(e->tree_cnt.ensure(hbl::wave_tree_counter_bytes((int)ncomb, (int)nw)));
@@ -1053,11 +885,10 @@ int combine_verify_split(hbh_engine* e, size_t ncomb, size_t m, const std::vecto
       HBH_CHECK(hbl::wave_verify(s2, (int)nchk, sd0, sd1, wflags, nullptr, (uint32_t*)e->fval.p));
       HBH_CHECK(hbl::wave_prod_fe(s2, (int)ncomb, (int)nw, (const uint32_t*)e->fval.p, dout + o_v));
     }
-    e->timer.end(s2, tp);
+    tp.stop();
     // engine stream, concurrently: the interpolation (lane-quad latency form, host digits)
-    hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
+    StageScope tm(e, s, HBH_STAGE_CURVE);
     HBH_CHECK(hbl::interp_g2_pair(s, (int)ncomb, (int)m, (const uint64_t*)(din + o_dg), din + o_q, e->ipart.p, dout));
-    e->timer.end(s, tm);
     return HBH_OK;
   };
   const int lrc = launch();
@@ -1067,14 +898,11 @@ int combine_verify_split(hbh_engine* e, size_t ncomb, size_t m, const std::vecto
     (void)hipStreamSynchronize(s2);
     (void)hipStreamSynchronize(s);
   }
-  if (!lrc && werr == hipSuccess) HBH_CHECK(hipMemcpyAsync(hs, dout, out_bytes, hipMemcpyDeviceToHost, s));
-  {
-    const int rc_ = end_call(e, s);
-    if (lrc) return lrc;
-    if (werr != hipSuccess) return fail(HBH_ERR_DEVICE, std::string("split check join: ") + hipGetErrorString(werr));
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(hipStreamSynchronize(s));
+  if (lrc) return lrc;
+  if (werr != hipSuccess) return fail(HBH_ERR_DEVICE, std::string("split check join: ") + hipGetErrorString(werr));
+  HBH_CHECK(download(s, hs, e->split_out, out_bytes));
+  const int frc = call.finish();
+  if (frc) return frc;
   std::memcpy(out, hs, ncomb * HBH_G2_BYTES);
   std::memcpy(verdicts, hs + o_v, ncomb);
   for (size_t c = 0; c < ncomb; c++) status[c] = lst[c];
@@ -1129,42 +957,30 @@ int hbh_combine_verify_g2(hbh_engine* e, size_t ncomb, int t, const uint32_t* id
   // P1 = master pk (one record per combine), P2 = the G1 generator (a flag, nothing uploaded)
   std::vector<uint8_t> p12(ncomb * HBH_G1_BYTES);
   for (size_t c = 0; c < ncomb; c++) std::memcpy(p12.data() + c * HBH_G1_BYTES, master_pk, HBH_G1_BYTES);
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(e->in_a.ensure(ncomb * m * 4));
-  HBH_CHECK(e->in_b.ensure(ncomb * m * HBH_G2_BYTES));
-  HBH_CHECK(e->in_q1.ensure(ncomb * HBH_G2_BYTES));
-  HBH_CHECK(e->in_p1.ensure(p12.size()));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, xs.data(), ncomb * m * 4));
+  HBH_CHECK(upload(s, e->in_b, shares, ncomb * m * HBH_G2_BYTES));
+  HBH_CHECK(upload(s, e->in_q1, hashes, ncomb * HBH_G2_BYTES));
+  HBH_CHECK(upload(s, e->in_p1, p12.data(), p12.size()));
   HBH_CHECK(e->out_x.ensure(ncomb * HBH_G2_BYTES));
   HBH_CHECK(e->status.ensure(ncomb * sizeof(int)));
   HBH_CHECK(e->out_v.ensure(ncomb));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, xs.data(), ncomb * m * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, shares, ncomb * m * HBH_G2_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_q1.p, hashes, ncomb * HBH_G2_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_p1.p, p12.data(), p12.size(), hipMemcpyHostToDevice, s));
   HBH_CHECK(hipMemsetAsync(e->status.p, 0, ncomb * sizeof(int), s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  rc = launch_combine_g2(e, s, ncomb, m, (const uint32_t*)e->in_a.p, e->in_b.p, e->out_x.p, (int*)e->status.p,
-                         xs.data());
-  if (rc) return rc;
-  e->timer.end(s, tm);
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    rc = launch_combine_g2(e, s, ncomb, m, (const uint32_t*)e->in_a.p, e->in_b.p, e->out_x.p, (int*)e->status.p,
+                           xs.data());
+    if (rc) return rc;
+  }
   rc = run_pairing_dev(e, s, ncomb, e->in_p1.p, e->in_q1.p, ncomb, nullptr, nullptr, e->out_x.p, ncomb, nullptr, 1,
                        (uint8_t*)e->out_v.p);
   if (rc) return rc;
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, ncomb * HBH_G2_BYTES, hipMemcpyDeviceToHost, s));
-  HBH_CHECK(hipMemcpyAsync(status, e->status.p, ncomb * sizeof(int), hipMemcpyDeviceToHost, s));
-  HBH_CHECK(hipMemcpyAsync(verdicts, e->out_v.p, ncomb, hipMemcpyDeviceToHost, s));
-  {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, ncomb * HBH_G2_BYTES));
+  HBH_CHECK(download(s, status, e->status, ncomb * sizeof(int)));
+  HBH_CHECK(download(s, verdicts, e->out_v, ncomb));
+  return call.finish();
 }
 
 int hbh_bivar_row(hbh_engine* e, size_t nrow, int t, size_t nparts, const uint8_t* commits, const uint32_t* part_idx,
@@ -1177,66 +993,26 @@ int hbh_bivar_row(hbh_engine* e, size_t nrow, int t, size_t nparts, const uint8_
   const size_t ncoef = (size_t)(t + 1) * (t + 2) / 2;
   for (size_t r = 0; r < nrow; r++)
     if (part_idx[r] >= nparts) return fail(HBH_ERR_ARG, "part index out of range");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   const size_t nout = nrow * (t + 1);
-  HBH_CHECK(e->in_a.ensure(nparts * ncoef * HBH_G1_BYTES));
-  HBH_CHECK(e->in_b.ensure(nrow * 4));
-  HBH_CHECK(e->in_c.ensure(nrow * 4));
+  HBH_CHECK(upload(s, e->in_a, commits, nparts * ncoef * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_b, part_idx, nrow * 4));
+  HBH_CHECK(upload(s, e->in_c, xs, nrow * 4));
   HBH_CHECK(e->out_x.ensure(nout * HBH_G1_BYTES));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, commits, nparts * ncoef * HBH_G1_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, part_idx, nrow * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_c.p, xs, nrow * 4, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::bivar_row(s, (int)nrow, t, e->in_a.p, (const uint32_t*)e->in_b.p, (const uint32_t*)e->in_c.p,
-                           e->out_x.p));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, nout * HBH_G1_BYTES, hipMemcpyDeviceToHost, s));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::bivar_row(s, (int)nrow, t, e->in_a.p, (const uint32_t*)e->in_b.p, (const uint32_t*)e->in_c.p,
+                             e->out_x.p));
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, nout * HBH_G1_BYTES));
+  return call.finish();
 }
 
 }  // extern "C"
 
 namespace {
-// Byte-level half of pairing 0.14's compressed decoding: flags (0x80 compressed, 0x40 infinity --
-// then 0xc0 || 0...0 exactly --, 0x20 larger y) and the big-endian -> little-endian word reversal.
-// The encoding holds nfe 48-byte field elements, highest Fp2 coefficient first (G2: x.c1 || x.c0);
-// words come out as coefficient 0 first (12 words each).
-void parse_compressed(const uint8_t* b, int nfe, uint32_t* words, uint8_t& f) {
-  f = 0;
-  if (!(b[0] & 0x80)) {
-    f = hbl::WIRE_REJECT;
-  } else if (b[0] & 0x40) {
-    bool zero = (b[0] & 0x3f) == 0;
-    for (int k = 1; k < 48 * nfe && zero; k++) zero = b[k] == 0;
-    f = zero ? hbl::WIRE_INFINITY : hbl::WIRE_REJECT;
-  } else if (b[0] & 0x20) {
-    f = hbl::WIRE_GREATEST;
-  }
-  for (int c = 0; c < nfe; c++) {
-    const uint8_t* e = b + 48 * (nfe - 1 - c);
-    for (int w = 0; w < 12; w++) {
-      uint32_t v = 0;
-      for (int k = 0; k < 4; k++) {
-        const int pos = 47 - (w * 4 + k);  // little-endian byte w*4+k of the element
-        const uint8_t byte = (e == b && pos == 0) ? (uint8_t)(b[0] & 0x1f) : e[pos];
-        v |= (uint32_t)byte << (8 * k);
-      }
-      words[c * 12 + w] = v;
-    }
-  }
-}
-
 // The decoder of one call: a forced form for every n; AUTO takes the latency form (k_wire_split.hip)
 // up to the group's threshold and the throughput form (k_wire.hip) above it.
 hipError_t launch_decompress(const hbh_engine* e, hipStream_t s, size_t n, bool g2, const uint32_t* xw,
@@ -1259,31 +1035,21 @@ int run_decompress(hbh_engine* e, size_t n, const uint8_t* in, uint8_t* out, uin
   std::vector<uint32_t> xw(n * 12 * nfe);
   std::vector<uint8_t> fl(n);
   for (size_t i = 0; i < n; i++) parse_compressed(in + i * 48 * nfe, nfe, xw.data() + i * 12 * nfe, fl[i]);
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(e->in_a.ensure(xw.size() * 4));
-  HBH_CHECK(e->in_b.ensure(n));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, xw.data(), xw.size() * 4));
+  HBH_CHECK(upload(s, e->in_b, fl.data(), n));
   HBH_CHECK(e->out_x.ensure(n * pb));
   HBH_CHECK(e->out_v.ensure(n));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, fl.data(), n, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(launch_decompress(e, s, n, g2, (const uint32_t*)e->in_a.p, (const uint8_t*)e->in_b.p, e->out_x.p,
-                              (uint8_t*)e->out_v.p));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, n * pb, hipMemcpyDeviceToHost, s));
-  HBH_CHECK(hipMemcpyAsync(ok, e->out_v.p, n, hipMemcpyDeviceToHost, s));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(launch_decompress(e, s, n, g2, (const uint32_t*)e->in_a.p, (const uint8_t*)e->in_b.p, e->out_x.p,
+                                (uint8_t*)e->out_v.p));
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, n * pb));
+  HBH_CHECK(download(s, ok, e->out_v, n));
+  return call.finish();
 }
 }  // namespace
 
@@ -1306,32 +1072,20 @@ int hbh_commitment_eval(hbh_engine* e, size_t n, int t, size_t ncommits, const u
   if (n > (size_t)1 << 28) return fail(HBH_ERR_ARG, "batch too large");
   for (size_t r = 0; r < n; r++)
     if (commit_idx[r] >= ncommits) return fail(HBH_ERR_ARG, "commitment index out of range");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  const size_t cbytes = ncommits * (size_t)(t + 1) * HBH_G1_BYTES;
-  HBH_CHECK(e->in_a.ensure(cbytes));
-  HBH_CHECK(e->in_b.ensure(n * 4));
-  HBH_CHECK(e->in_c.ensure(n * 4));
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, commits, ncommits * (size_t)(t + 1) * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_b, commit_idx, n * 4));
+  HBH_CHECK(upload(s, e->in_c, xs, n * 4));
   HBH_CHECK(e->out_x.ensure(n * HBH_G1_BYTES));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, commits, cbytes, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_b.p, commit_idx, n * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_c.p, xs, n * 4, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::commit_eval(s, (int)n, t, e->in_a.p, (const uint32_t*)e->in_b.p, (const uint32_t*)e->in_c.p,
-                             e->out_x.p));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, n * HBH_G1_BYTES, hipMemcpyDeviceToHost, s));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::commit_eval(s, (int)n, t, e->in_a.p, (const uint32_t*)e->in_b.p, (const uint32_t*)e->in_c.p,
+                               e->out_x.p));
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, out, e->out_x, n * HBH_G1_BYTES));
+  return call.finish();
 }
 
 int hbh_bivar_ack_check(hbh_engine* e, size_t nack, int t, size_t nparts, const uint8_t* commits,
@@ -1344,36 +1098,18 @@ int hbh_bivar_ack_check(hbh_engine* e, size_t nack, int t, size_t nparts, const 
   if (!commits || !part_idx || !xs || !ys || !vals || !verdicts) return fail(HBH_ERR_ARG, "null pointer");
   const size_t ncoef = (size_t)(t + 1) * (t + 2) / 2;
   // one row(x) per distinct (part, x): evaluate(x, y) = sum_j row(x)_j y^j
-  std::vector<uint32_t> row_part, row_x, row_of(nack);
-  {
-    std::unordered_map<uint64_t, uint32_t> seen;
-    seen.reserve(nack < 4096 ? nack : 4096);
-    for (size_t a = 0; a < nack; a++) {
-      if (part_idx[a] >= nparts) return fail(HBH_ERR_ARG, "part index out of range");
-      const uint64_t key = ((uint64_t)part_idx[a] << 32) | xs[a];
-      auto it = seen.emplace(key, (uint32_t)row_part.size());
-      if (it.second) {
-        row_part.push_back(part_idx[a]);
-        row_x.push_back(xs[a]);
-      }
-      row_of[a] = it.first->second;
-    }
-  }
+  std::vector<uint32_t> row_part, row_x, row_of;
+  if (!dedup_rows(nack, nparts, part_idx, xs, row_part, row_x, row_of))
+    return fail(HBH_ERR_ARG, "part index out of range");
   const size_t nrow = row_part.size();
-  // acks in order of y: the lanes of a wave then run the same small-scalar double-and-add
-  std::vector<uint32_t> order(nack);
-  for (size_t a = 0; a < nack; a++) order[a] = (uint32_t)a;
-  std::stable_sort(order.begin(), order.end(), [ys](uint32_t i, uint32_t j) { return ys[i] < ys[j]; });
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  {
-    const int rc_ = begin_call(e, s);
-    if (rc_) return rc_;
-  }
-  HBH_CHECK(e->in_a.ensure(nparts * ncoef * HBH_G1_BYTES));
+  std::vector<uint32_t> order;
+  order_by_y(nack, ys, order);
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(upload(s, e->in_a, commits, nparts * ncoef * HBH_G1_BYTES));
   HBH_CHECK(e->in_b.ensure(nrow * 8 + nack * 12));
-  HBH_CHECK(e->in_c.ensure(nack * HBH_FR_BYTES));
+  HBH_CHECK(upload(s, e->in_c, vals, nack * HBH_FR_BYTES));
   HBH_CHECK(e->work.ensure(hbl::bivar_rows_quad_bytes((int)nrow, t)));
   HBH_CHECK(e->out_v.ensure(nack));
   uint32_t* d_rp = (uint32_t*)e->in_b.p;
@@ -1381,27 +1117,21 @@ int hbh_bivar_ack_check(hbh_engine* e, size_t nack, int t, size_t nparts, const 
   uint32_t* d_ro = d_rx + nrow;
   uint32_t* d_y = d_ro + nack;
   uint32_t* d_ord = d_y + nack;
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, commits, nparts * ncoef * HBH_G1_BYTES, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_rp, row_part.data(), nrow * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_rx, row_x.data(), nrow * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_ro, row_of.data(), nack * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_y, ys, nack * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_ord, order.data(), nack * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_c.p, vals, nack * HBH_FR_BYTES, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::bivar_row_quad(s, (int)nrow, t, e->in_a.p, d_rp, d_rx, e->work.p));
-  rc = ensure_fbtab(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hbl::bivar_check_quad(s, (int)nack, t, e->work.p, d_ro, d_y, (const uint32_t*)e->in_c.p, e->fbtab.p,
-                                  (uint8_t*)e->out_v.p, d_ord));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(verdicts, e->out_v.p, nack, hipMemcpyDeviceToHost, s));
+  HBH_CHECK(h2d(s, d_rp, row_part.data(), nrow * 4));
+  HBH_CHECK(h2d(s, d_rx, row_x.data(), nrow * 4));
+  HBH_CHECK(h2d(s, d_ro, row_of.data(), nack * 4));
+  HBH_CHECK(h2d(s, d_y, ys, nack * 4));
+  HBH_CHECK(h2d(s, d_ord, order.data(), nack * 4));
   {
-    const int rc_ = end_call(e, s);
-    if (rc_) return rc_;
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::bivar_row_quad(s, (int)nrow, t, e->in_a.p, d_rp, d_rx, e->work.p));
+    rc = ensure_fbtab(e, s);
+    if (rc) return rc;
+    HBH_CHECK(hbl::bivar_check_quad(s, (int)nack, t, e->work.p, d_ro, d_y, (const uint32_t*)e->in_c.p, e->fbtab.p,
+                                    (uint8_t*)e->out_v.p, d_ord));
   }
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(download(s, verdicts, e->out_v, nack));
+  return call.finish();
 }
 
 }  // extern "C"
@@ -1410,8 +1140,6 @@ int hbh_bivar_ack_check(hbh_engine* e, size_t nack, int t, size_t nparts, const 
 // Inputs and outputs in device memory, asynchronous on `stream` (NULL = engine stream), ordered
 // after the engine's previous call like hbh_verify_pairing_eq_dev.
 namespace {
-hipStream_t dev_stream(hbh_engine* e, void* stream) { return stream ? (hipStream_t)stream : e->stream; }
-
 int run_interp_dev(hbh_engine* e, void* stream, size_t ncomb, int t, const uint32_t* d_idx, const void* d_pts,
                    void* d_out, int* d_status, bool g2) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
@@ -1421,24 +1149,18 @@ int run_interp_dev(hbh_engine* e, void* stream, size_t ncomb, int t, const uint3
   if (!d_idx || !d_pts || !d_out || !d_status) return fail(HBH_ERR_ARG, "null pointer");
   const size_t m = (size_t)t + 1;
   if (ncomb * m > (size_t)1 << 26) return fail(HBH_ERR_ARG, "batch too large");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = dev_stream(e, stream);
-  rc = begin_call(e, s);
-  if (rc) return rc;
+  EngineCall call(e, stream, false);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   HBH_CHECK(e->in_a.ensure(ncomb * m * 4));
   HBH_CHECK(hipMemsetAsync(d_status, 0, ncomb * sizeof(int), s));
   HBH_CHECK(hbl::index_plus_one(s, (int)(ncomb * m), (int)m, d_idx, (uint32_t*)e->in_a.p, d_status));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  if (g2) {
-    rc = launch_combine_g2(e, s, ncomb, m, (const uint32_t*)e->in_a.p, d_pts, d_out, d_status);
-    if (rc) return rc;
-  } else {
-    rc = launch_combine_g1(e, s, ncomb, m, (const uint32_t*)e->in_a.p, d_pts, d_out, d_status);
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    rc = launch_combine(e, s, g2, ncomb, m, (const uint32_t*)e->in_a.p, d_pts, d_out, d_status);
     if (rc) return rc;
   }
-  e->timer.end(s, tm);
-  return end_call(e, s);
+  return call.finish();
 }
 
 int run_decompress_dev(hbh_engine* e, void* stream, size_t n, const uint8_t* d_in, void* d_out, uint8_t* d_ok,
@@ -1448,24 +1170,20 @@ int run_decompress_dev(hbh_engine* e, void* stream, size_t n, const uint8_t* d_i
   if (!d_in || !d_out || !d_ok) return fail(HBH_ERR_ARG, "null pointer");
   if (n > (size_t)1 << 28) return fail(HBH_ERR_ARG, "batch too large");
   const int nfe = g2 ? 2 : 1;
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = dev_stream(e, stream);
   // a staging slot of its own: wait for the last general call and this slot's previous user only
-  const int slot = e->wire_slot;
-  e->wire_slot ^= 1;
-  HBH_CHECK(hipStreamWaitEvent(s, e->done, 0));
-  HBH_CHECK(hipStreamWaitEvent(s, e->wire_done[slot], 0));
-  HBH_CHECK(e->wire_w[slot].ensure(n * 12 * nfe * 4));
-  HBH_CHECK(e->wire_f[slot].ensure(n));
-  uint32_t* xw = (uint32_t*)e->wire_w[slot].p;
-  uint8_t* fl = (uint8_t*)e->wire_f[slot].p;
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::wire_parse(s, (int)n, nfe, d_in, xw, fl));
-  HBH_CHECK(launch_decompress(e, s, n, g2, xw, fl, d_out, d_ok));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipEventRecord(e->wire_done[slot], s));
-  return HBH_OK;
+  EngineCall call(e, stream, false, EngineCall::WIRE_SLOT);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  HBH_CHECK(e->wire_w[call.slot].ensure(n * 12 * nfe * 4));
+  HBH_CHECK(e->wire_f[call.slot].ensure(n));
+  uint32_t* xw = (uint32_t*)e->wire_w[call.slot].p;
+  uint8_t* fl = (uint8_t*)e->wire_f[call.slot].p;
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::wire_parse(s, (int)n, nfe, d_in, xw, fl));
+    HBH_CHECK(launch_decompress(e, s, n, g2, xw, fl, d_out, d_ok));
+  }
+  return call.finish();
 }
 }  // namespace
 
@@ -1495,20 +1213,19 @@ int hbh_bivar_ack_check_dev(hbh_engine* e, void* stream, size_t nack, int t, con
   if (nack == 0) return HBH_OK;
   if (!d_commits || !d_row_part || !d_row_x || !d_row_of || !d_ys || !d_vals || !d_verdicts || nrow == 0)
     return fail(HBH_ERR_ARG, "null pointer");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = dev_stream(e, stream);
-  rc = begin_call(e, s);
-  if (rc) return rc;
+  EngineCall call(e, stream, false);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   HBH_CHECK(e->work.ensure(hbl::bivar_rows_quad_bytes((int)nrow, t)));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::bivar_row_quad(s, (int)nrow, t, d_commits, d_row_part, d_row_x, e->work.p));
-  rc = ensure_fbtab(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hbl::bivar_check_quad(s, (int)nack, t, e->work.p, d_row_of, d_ys, (const uint32_t*)d_vals, e->fbtab.p,
-                                  d_verdicts, nullptr));
-  e->timer.end(s, tm);
-  return end_call(e, s);
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::bivar_row_quad(s, (int)nrow, t, d_commits, d_row_part, d_row_x, e->work.p));
+    rc = ensure_fbtab(e, s);
+    if (rc) return rc;
+    HBH_CHECK(hbl::bivar_check_quad(s, (int)nack, t, e->work.p, d_row_of, d_ys, (const uint32_t*)d_vals, e->fbtab.p,
+                                    d_verdicts, nullptr));
+  }
+  return call.finish();
 }
 
 }  // extern "C"
@@ -1522,24 +1239,19 @@ int hbh_g1_mul_gen(hbh_engine* e, size_t n, const uint8_t* scalars, uint8_t* out
   if (n == 0) return HBH_OK;
   if (!scalars || !out) return fail(HBH_ERR_ARG, "null pointer");
   if (n > (size_t)1 << 28) return fail(HBH_ERR_ARG, "batch too large");
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  int rc = begin_call(e, s);
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  int rc = ensure_fbtab(e, s);
   if (rc) return rc;
-  rc = ensure_fbtab(e, s);
-  if (rc) return rc;
-  HBH_CHECK(e->in_a.ensure(n * 32));
+  HBH_CHECK(upload(s, e->in_a, scalars, n * 32));
   HBH_CHECK(e->out_x.ensure(n * HBH_G1_BYTES));
-  HBH_CHECK(hipMemcpyAsync(e->in_a.p, scalars, n * 32, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::g1_mul_gen(s, (int)n, e->fbtab.p, (const uint32_t*)e->in_a.p, e->out_x.p));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, n * HBH_G1_BYTES, hipMemcpyDeviceToHost, s));
-  rc = end_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::g1_mul_gen(s, (int)n, e->fbtab.p, (const uint32_t*)e->in_a.p, e->out_x.p));
+  }
+  HBH_CHECK(download(s, out, e->out_x, n * HBH_G1_BYTES));
+  return call.finish();
 }
 
 }  // extern "C"
@@ -1632,15 +1344,15 @@ int set_rows(hbh_commit_set* cs, hipStream_t s, bool affine, size_t n, const uin
     if (rc) return rc;
     HBH_CHECK(cs->stage.ensure(np.size() * 8));
     uint32_t* d_p = (uint32_t*)cs->stage.p;
-    HBH_CHECK(hipMemcpyAsync(d_p, np.data(), np.size() * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_p + np.size(), nx.data(), nx.size() * 4, hipMemcpyHostToDevice, s));
-    hipEvent_t tm = cs->e->timer.begin(s, HBH_STAGE_CURVE, cs->e->profiling);
+    HBH_CHECK(h2d(s, d_p, np.data(), np.size() * 4));
+    HBH_CHECK(h2d(s, d_p + np.size(), nx.data(), nx.size() * 4));
+    StageScope tm(cs->e, s, HBH_STAGE_CURVE);
     void* dst = (uint8_t*)R.p + first * row_bytes;
     if (affine)
       HBH_CHECK(hbl::bivar_row(s, (int)np.size(), cs->t, cs->commits, d_p, d_p + np.size(), dst));
     else
       HBH_CHECK(hbl::bivar_row_quad(s, (int)np.size(), cs->t, cs->commits, d_p, d_p + np.size(), dst));
-    cs->e->timer.end(s, tm);
+    tm.stop();
     // the staged indices are read by the kernel: the host vectors die at return
     HBH_CHECK(hipStreamSynchronize(s));
     return HBH_OK;
@@ -1652,87 +1364,6 @@ int set_rows(hbh_commit_set* cs, hipStream_t s, bool affine, size_t n, const uin
   }
   R.n = first + np.size();
   return HBH_OK;
-}
-
-// Finite-difference plan of an Ack drain (hbl::bivar_fd): a row slot whose acks form a dense run of y
-// -- at least 2 (t + 1) acks spanning at most twice as many consecutive y, as a node's drain has (one
-// Ack per sender per Part) -- is evaluated at every y of its span from the difference table at y0 (the
-// seed levels: (t+1)(t+2)/2 small products) and t additions per further y; its acks then compare
-// against those points (epos).  y0 = 0 when the run starts at y <= t + 1 (the seed's products are then
-// one per entry, worth the few extra steps), else the run's first y.  Every other ack takes the Horner
-// kernel (other, in order of y).  FD rows are sorted by span length (the run kernel's workgroups step
-// their rows together); a span is at least 2 (t + 1) points (the seed's two tables live in it).
-struct FdPlan {
-  std::vector<uint32_t> slot, y0, off, len;  // per FD row
-  std::vector<uint32_t> epos;                // per ack (FD acks only)
-  std::vector<uint32_t> fd_acks, other;      // ack lists
-  size_t npts = 0;                           // E points of all FD rows
-};
-void plan_fd(size_t n, const std::vector<uint32_t>& slot, const uint32_t* ys, int t, FdPlan& P) {
-  const uint64_t T1 = (uint64_t)t + 1;
-  uint32_t nslot = 0;
-  for (size_t a = 0; a < n; a++) nslot = std::max(nslot, slot[a] + 1);
-  std::vector<uint32_t> cnt(nslot, 0), ymin(nslot, 0xffffffffu), ymax(nslot, 0);
-  for (size_t a = 0; a < n; a++) {
-    const uint32_t s = slot[a];
-    cnt[s]++;
-    ymin[s] = std::min(ymin[s], ys[a]);
-    ymax[s] = std::max(ymax[s], ys[a]);
-  }
-  std::vector<uint32_t> cand;
-  for (uint32_t s = 0; s < nslot; s++) {
-    if (!cnt[s] || T1 > 128) continue;
-    if (ymin[s] <= T1) ymin[s] = 0;  // seed at y0 = 0
-    const uint64_t span = (uint64_t)ymax[s] - ymin[s] + 1;
-    if (cnt[s] >= 2 * T1 && span >= 2 * T1 && span <= 2 * (uint64_t)cnt[s] && span < ((uint64_t)1 << 20))
-      cand.push_back(s);
-  }
-  std::stable_sort(cand.begin(), cand.end(), [&](uint32_t a, uint32_t b) {
-    const uint32_t la = ymax[a] - ymin[a], lb = ymax[b] - ymin[b];
-    return la != lb ? la > lb : ymin[a] < ymin[b];
-  });
-  std::vector<int32_t> fd_of(nslot, -1);
-  for (uint32_t s : cand) {
-    fd_of[s] = (int32_t)P.slot.size();
-    P.slot.push_back(s);
-    P.y0.push_back(ymin[s]);
-    P.off.push_back((uint32_t)P.npts);
-    P.len.push_back(ymax[s] - ymin[s] + 1);  // >= 2 (t + 1)
-    P.npts += ymax[s] - ymin[s] + 1;
-  }
-  P.epos.assign(n, 0);
-  for (size_t a = 0; a < n; a++) {
-    const int32_t f = fd_of[slot[a]];
-    if (f < 0) {
-      P.other.push_back((uint32_t)a);
-    } else {
-      P.epos[a] = P.off[f] + (ys[a] - P.y0[f]);
-      P.fd_acks.push_back((uint32_t)a);
-    }
-  }
-}
-
-// Acks in order of y (stable): the lanes of a wave then run the same small-scalar double-and-add.
-// y is a node index + 1, so a counting sort does it in O(n) (10^6 acks of a network-wide check).
-// Round 4 measured (row tile, y) orders, whose waves re-read one tile's rows while they sit in L2:
-// HBM traffic per 10^6 acks falls from 4.68 GB (this order) to 0.74 GB (tiles of 256 row slots) and
-// 0.24 GB (1,024), but the launch is SLOWER at every tile size -- 54.2 ms here, 57.5 (64), 61.8-62.2
-// (256), 60.6-60.8 (1,024), 57.4 (4,096) (profiles/r04/c11_ack_tile_traffic.txt; with an XCD-
-// contiguous workgroup map as well: 57.5-58.2 ms, c3_ab.txt).  The kernel is VALU-bound at two
-// waves per SIMD (255 VGPRs) and its row fetches overlap the Horner arithmetic, so this order stays.
-void order_by_y(size_t n, const uint32_t* ys, std::vector<uint32_t>& order) {
-  order.resize(n);
-  uint32_t ymax = 0;
-  for (size_t a = 0; a < n; a++) ymax = std::max(ymax, ys[a]);
-  if (ymax < (1u << 20)) {
-    std::vector<uint32_t> start((size_t)ymax + 2, 0);
-    for (size_t a = 0; a < n; a++) start[(size_t)ys[a] + 1]++;
-    for (size_t y = 1; y < start.size(); y++) start[y] += start[y - 1];
-    for (size_t a = 0; a < n; a++) order[start[ys[a]]++] = (uint32_t)a;
-    return;
-  }
-  for (size_t a = 0; a < n; a++) order[a] = (uint32_t)a;
-  std::stable_sort(order.begin(), order.end(), [ys](uint32_t i, uint32_t j) { return ys[i] < ys[j]; });
 }
 
 int check_parts(const hbh_commit_set* cs, size_t n, const uint32_t* part_idx) {
@@ -1783,18 +1414,15 @@ int hbh_commit_set_add(hbh_commit_set* cs, size_t nparts, const uint8_t* commits
   if (!commits) return fail(HBH_ERR_ARG, "null pointer");
   if (cs->nparts + nparts > ((size_t)1 << 24)) return fail(HBH_ERR_ARG, "too many commitments");
   hbh_engine* e = cs->e;
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  int rc = begin_call(e, s);
-  if (rc) return rc;
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   const size_t cb = cs->ncoef * HBH_G1_BYTES;
-  rc = grow_keep(s, &cs->commits, &cs->commits_cap, cs->nparts * cb, (cs->nparts + nparts) * cb);
+  int rc = grow_keep(s, &cs->commits, &cs->commits_cap, cs->nparts * cb, (cs->nparts + nparts) * cb);
   if (rc) return rc;
-  HBH_CHECK(hipMemcpyAsync((uint8_t*)cs->commits + cs->nparts * cb, commits, nparts * cb, hipMemcpyHostToDevice, s));
-  rc = end_call(e, s);
+  HBH_CHECK(h2d(s, (uint8_t*)cs->commits + cs->nparts * cb, commits, nparts * cb));
+  rc = call.finish();
   if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
   cs->nparts += nparts;
   return HBH_OK;
 }
@@ -1815,25 +1443,21 @@ int hbh_bivar_row_set(hbh_commit_set* cs, size_t nrow, const uint32_t* part_idx,
   if (rc) return rc;
   hbh_engine* e = cs->e;
   const int t = cs->t;
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  rc = begin_call(e, s);
-  if (rc) return rc;
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   const size_t nout = nrow * (t + 1);
   HBH_CHECK(e->in_b.ensure(nrow * 8));
   HBH_CHECK(e->out_x.ensure(nout * HBH_G1_BYTES));
   uint32_t* d_p = (uint32_t*)e->in_b.p;
-  HBH_CHECK(hipMemcpyAsync(d_p, part_idx, nrow * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_p + nrow, xs, nrow * 4, hipMemcpyHostToDevice, s));
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
-  HBH_CHECK(hbl::bivar_row(s, (int)nrow, t, cs->commits, d_p, d_p + nrow, e->out_x.p));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(out, e->out_x.p, nout * HBH_G1_BYTES, hipMemcpyDeviceToHost, s));
-  rc = end_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  HBH_CHECK(h2d(s, d_p, part_idx, nrow * 4));
+  HBH_CHECK(h2d(s, d_p + nrow, xs, nrow * 4));
+  {
+    StageScope tm(e, s, HBH_STAGE_CURVE);
+    HBH_CHECK(hbl::bivar_row(s, (int)nrow, t, cs->commits, d_p, d_p + nrow, e->out_x.p));
+  }
+  HBH_CHECK(download(s, out, e->out_x, nout * HBH_G1_BYTES));
+  return call.finish();
 }
 
 int hbh_bivar_ack_check_set(hbh_commit_set* cs, size_t nack, const uint32_t* part_idx, const uint32_t* xs,
@@ -1848,11 +1472,9 @@ int hbh_bivar_ack_check_set(hbh_commit_set* cs, size_t nack, const uint32_t* par
   std::vector<uint32_t> order;
   hbh_engine* e = cs->e;
   const int t = cs->t;
-  std::lock_guard<std::mutex> lk(e->mu);
-  HBH_CHECK(hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  rc = begin_call(e, s);
-  if (rc) return rc;
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
   // lane quads (four lanes per ack, one wave per SIMD) for latency; one lane per ack on affine
   // rows (two waves per SIMD, mixed additions) for throughput
   const bool lane = e->ack_impl == HBH_ACK_LANE || e->ack_impl == HBH_ACK_LANE_HORNER ||
@@ -1872,15 +1494,14 @@ int hbh_bivar_ack_check_set(hbh_commit_set* cs, size_t nack, const uint32_t* par
     order_by_y(nack, ys, order);
   }
   HBH_CHECK(e->in_b.ensure(nack * 12));
-  HBH_CHECK(e->in_c.ensure(nack * HBH_FR_BYTES));
   HBH_CHECK(e->out_v.ensure(nack));
   uint32_t* d_ro = (uint32_t*)e->in_b.p;
   uint32_t* d_y = d_ro + nack;
   uint32_t* d_ord = d_y + nack;
-  HBH_CHECK(hipMemcpyAsync(d_ro, slot.data(), nack * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(d_y, ys, nack * 4, hipMemcpyHostToDevice, s));
-  if (!order.empty()) HBH_CHECK(hipMemcpyAsync(d_ord, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
-  HBH_CHECK(hipMemcpyAsync(e->in_c.p, vals, nack * HBH_FR_BYTES, hipMemcpyHostToDevice, s));
+  HBH_CHECK(h2d(s, d_ro, slot.data(), nack * 4));
+  HBH_CHECK(h2d(s, d_y, ys, nack * 4));
+  if (!order.empty()) HBH_CHECK(h2d(s, d_ord, order.data(), order.size() * 4));
+  HBH_CHECK(upload(s, e->in_c, vals, nack * HBH_FR_BYTES));
   rc = ensure_fbtab(e, s);
   if (rc) return rc;
   if (!fd.slot.empty() && ensure_fb16(e, s) != HBH_OK) {
@@ -1900,14 +1521,14 @@ int hbh_bivar_ack_check_set(hbh_commit_set* cs, size_t nack, const uint32_t* par
     HBH_CHECK(e->fd_meta.ensure(words * 4));
     HBH_CHECK(e->fd_e.ensure(fd.npts * hbl::fd_point_bytes()));
     d_fd = (uint32_t*)e->fd_meta.p;
-    HBH_CHECK(hipMemcpyAsync(d_fd, fd.slot.data(), nfd * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_fd + nfd, fd.y0.data(), nfd * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_fd + 2 * nfd, fd.off.data(), nfd * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_fd + 3 * nfd, fd.len.data(), nfd * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_fd + 4 * nfd, fd.epos.data(), nack * 4, hipMemcpyHostToDevice, s));
-    HBH_CHECK(hipMemcpyAsync(d_fd + 4 * nfd + nack, fd.fd_acks.data(), fd.fd_acks.size() * 4, hipMemcpyHostToDevice, s));
+    HBH_CHECK(h2d(s, d_fd, fd.slot.data(), nfd * 4));
+    HBH_CHECK(h2d(s, d_fd + nfd, fd.y0.data(), nfd * 4));
+    HBH_CHECK(h2d(s, d_fd + 2 * nfd, fd.off.data(), nfd * 4));
+    HBH_CHECK(h2d(s, d_fd + 3 * nfd, fd.len.data(), nfd * 4));
+    HBH_CHECK(h2d(s, d_fd + 4 * nfd, fd.epos.data(), nack * 4));
+    HBH_CHECK(h2d(s, d_fd + 4 * nfd + nack, fd.fd_acks.data(), fd.fd_acks.size() * 4));
   }
-  hipEvent_t tm = e->timer.begin(s, HBH_STAGE_CURVE, e->profiling);
+  StageScope tm(e, s, HBH_STAGE_CURVE);
   if (lane && nfd) {
     HBH_CHECK(hbl::bivar_fd(s, (int)nfd, t, cs->rows[1].p, d_fd, d_fd + nfd, d_fd + 2 * nfd, d_fd + 3 * nfd,
                             e->fd_e.p));
@@ -1921,12 +1542,9 @@ int hbh_bivar_ack_check_set(hbh_commit_set* cs, size_t nack, const uint32_t* par
   else
     HBH_CHECK(hbl::bivar_check_quad(s, (int)nack, t, cs->rows[0].p, d_ro, d_y, (const uint32_t*)e->in_c.p,
                                     e->fbtab.p, (uint8_t*)e->out_v.p, d_ord));
-  e->timer.end(s, tm);
-  HBH_CHECK(hipMemcpyAsync(verdicts, e->out_v.p, nack, hipMemcpyDeviceToHost, s));
-  rc = end_call(e, s);
-  if (rc) return rc;
-  HBH_CHECK(hipStreamSynchronize(s));
-  return HBH_OK;
+  tm.stop();
+  HBH_CHECK(download(s, verdicts, e->out_v, nack));
+  return call.finish();
 }
 
 }  // extern "C"

@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(128, WPS) k_g2_decompress(int n, const uint32_
 }
 
 // Byte-level half of the decoding on the device, for encodings already in HBM (the _dev entry
-// points): the same flag rules and word reversal as the host's parse_compressed (engine.hip).
+// points): the same flag rules and word reversal as the host's parse_compressed (wire_host.hpp).
 // One thread per encoding of nfe 48-byte big-endian field elements.
 __global__ void __launch_bounds__(256) k_wire_parse(int n, int nfe, const uint8_t* __restrict__ in,
                                                     uint32_t* __restrict__ xw, uint8_t* __restrict__ flags) {

@@ -5,12 +5,9 @@
 
 #include <cstdint>
 
-namespace hbl {
+#include "wire_host.hpp"  // hbl::WIRE_* flags, parse_compressed
 
-// per-point flags prepared by the host from the compressed encoding's top bits
-constexpr uint8_t WIRE_INFINITY = 1;  // valid encoding of the point at infinity
-constexpr uint8_t WIRE_GREATEST = 2;  // the "y is the larger root" bit
-constexpr uint8_t WIRE_REJECT = 4;    // malformed flags (not compressed, bad infinity encoding)
+namespace hbl {
 
 // G1Compressed::into_affine for n points: xw = 12 canonical LE words of x per point (flag bits
 // cleared); out = ABI G1 points (all-zero when ok[i] == 0 or for infinity); ok[i] = 1 iff the
