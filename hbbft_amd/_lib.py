@@ -88,6 +88,8 @@ SIGNATURES = [
 ]
 STAGE_PREPARE, STAGE_PAIRING, STAGE_CURVE = 0, 1, 2
 IMPL_AUTO, IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT, IMPL_WAVE2 = 3, 4, 5, 6, 7, 8   # HBH_IMPL_* (0, 1, 2 = retired THREAD, LANE_COOP, THREAD_SIGNED)
+IMPL_WAVEP = 10  # HBH_IMPL_WAVEP (9 is not assigned)
+AUTO_WAVEP_MIN, AUTO_WAVEP_MAX = 1025, 1536  # HBH_AUTO_WAVEP_* (profiles/r08: the sizes where WAVEP beats WAVE by more than the spread)
 ACK_AUTO, ACK_QUAD, ACK_LANE, ACK_LANE_HORNER = 0, 1, 2, 3  # HBH_ACK_*
 DEC_AUTO, DEC_LANE, DEC_SPLIT = 0, 1, 2  # HBH_DEC_*
 AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPLIT_MAX

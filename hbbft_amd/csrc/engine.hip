@@ -264,6 +264,7 @@ struct StageScope {
 
 int resolve_impl(const hbh_engine* e, size_t n) {
   if (e->impl != HBH_IMPL_AUTO) return e->impl;
+  if (n >= HBH_AUTO_WAVEP_MIN && n <= HBH_AUTO_WAVEP_MAX) return HBH_IMPL_WAVEP;
   if (n <= HBH_AUTO_WAVE2_MAX) return HBH_IMPL_WAVE2;
   if (n <= HBH_AUTO_WAVE_MAX) return HBH_IMPL_WAVE;
   if (n <= HBH_AUTO_OCT_MAX) return HBH_IMPL_OCT;
@@ -299,6 +300,7 @@ hipError_t verify_kind(int kind, hipStream_t s, int n, const hbl::PairSideDesc& 
                        int flags, uint8_t* v, uint32_t* val) {
   if (kind == HBH_IMPL_WAVE2) return wave2_verify(s, n, a, b, flags, v, val);
   if (kind == HBH_IMPL_WAVE) return hbl::wave_verify(s, n, a, b, flags, v, val);
+  if (kind == HBH_IMPL_WAVEP) return hbl::wavep_verify(s, n, a, b, flags, v, val);
   if (kind == HBH_IMPL_QUAD) return hbl::quad_verify(s, n, a, b, flags, v, val);
   if (kind == HBH_IMPL_OCT) return hbl::oct_verify(s, n, a, b, flags, v, val);
   return hbl::pair_verify(s, n, a, b, flags, v, val);
@@ -309,7 +311,7 @@ hipError_t verify_kind(int kind, hipStream_t s, int n, const hbl::PairSideDesc& 
 // size -- above HBH_AUTO_SPLIT_HI one more (partial) PAIR round; above HBH_AUTO_SPLIT_LO PAIR on
 // HBH_AUTO_SPLIT_LO checks (one wave per SIMD) first; what is left runs on WAVE up to
 // HBH_AUTO_WAVE_MAX, OCT up to HBH_AUTO_OCT_MAX, QUAD up to HBH_AUTO_QUAD_MAX, PAIR (one wave per
-// SIMD) above.  A partial
+// SIMD) above; a remainder in [HBH_AUTO_WAVEP_MIN, HBH_AUTO_WAVEP_MAX] runs on WAVEP first.  A partial
 // lane-pair round costs as much as a full one once any SIMD needs a second wave (40,960 checks:
 // PAIR alone 20.5-20.7 ms, PAIR + QUAD 19.4 ms, profiles/r04/c20_auto_split.txt).
 hipError_t verify_auto(hipStream_t s, size_t n, const hbl::PairSideDesc& s1, const hbl::PairSideDesc& s2, int flags,
@@ -337,6 +339,7 @@ hipError_t verify_auto(hipStream_t s, size_t n, const hbl::PairSideDesc& s1, con
     off += HBH_AUTO_SPLIT_LO;
     rem -= HBH_AUTO_SPLIT_LO;
   }
+  if (rem >= HBH_AUTO_WAVEP_MIN && rem <= HBH_AUTO_WAVEP_MAX) return at(off, rem, HBH_IMPL_WAVEP);
   if (rem <= HBH_AUTO_WAVE2_MAX) return at(off, rem, HBH_IMPL_WAVE2);
   if (rem <= HBH_AUTO_WAVE_MAX) return at(off, rem, HBH_IMPL_WAVE);
   if (rem <= HBH_AUTO_OCT_MAX) return at(off, rem, HBH_IMPL_OCT);
@@ -357,9 +360,10 @@ int launch_pair(hbh_engine* e, hipStream_t s, int impl, size_t n, const void* d_
     // WAVE2 walks every side: a table costs a serial 68-step walk (k_oct_prep, ~0.5 ms) before the
     // first check.  WAVE tables both sides of a call of >= HBH_WAVE_TT_MIN checks when both are
     // shared (decryption shares: H_uv and W per ciphertext): its TT program takes 138 Miller stages
-    // where walking both sides takes 211 (round 6); one walked side gains nothing (TW: 210).
+    // where walking both sides takes 211 (round 6); one walked side gains nothing (TW: 210).  WAVEP
+    // runs the same programs and follows the same rule.
     if (!tab_ok[k] || impl == HBH_IMPL_WAVE2) continue;
-    if (impl == HBH_IMPL_WAVE && !(tab_ok[0] && tab_ok[1] && n >= HBH_WAVE_TT_MIN)) continue;
+    if ((impl == HBH_IMPL_WAVE || impl == HBH_IMPL_WAVEP) && !(tab_ok[0] && tab_ok[1] && n >= HBH_WAVE_TT_MIN)) continue;
     HBH_CHECK(tab[k]->ensure(hbl::pair_table_bytes(sd[k].nq)));
     HBH_CHECK(inf[k]->ensure(sd[k].nq));
     StageScope tm(e, s, HBH_STAGE_PREPARE);
@@ -581,7 +585,7 @@ int hbh_dbg_pairing(hbh_engine* e, size_t n, const uint8_t* p, const uint8_t* q,
 int hbh_engine_set_pairing_impl(hbh_engine* e, int impl) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (impl != HBH_IMPL_PAIR && impl != HBH_IMPL_AUTO && impl != HBH_IMPL_WAVE && impl != HBH_IMPL_QUAD &&
-      impl != HBH_IMPL_OCT && impl != HBH_IMPL_WAVE2)
+      impl != HBH_IMPL_OCT && impl != HBH_IMPL_WAVE2 && impl != HBH_IMPL_WAVEP)
     return fail(HBH_ERR_ARG, "unknown or retired pairing implementation");
   std::lock_guard<std::mutex> lk(e->mu);
   e->impl = impl;

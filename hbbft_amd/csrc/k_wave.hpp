@@ -4,17 +4,65 @@
 //   WV_PROG    the namespace of the stage programs (hbw from wave_prog.inc / hbw64 from wave_prog64.inc),
 //   WV_THREADS threads per check (64 / 128),
 //   WV_FULL    1: the Miller-only, tree and product modes of the split master check (32-pair set only).
+//   WV_PACKED  1 (k_wavep.hip, with WV_THREADS 64): a workgroup is WV_PACK waves, wave w running check
+//              blockIdx.x * WV_PACK + w in its own LDS region; the cyclotomic-squaring runs and the
+//              inversion of all its checks run together on one wave (cyc_run_packed; wave 0, or the
+//              waves in turn with WV_PACK_ROTATE).  No wave leaves
+//              before the last workgroup barrier: a slot past n or a check with an index out of range
+//              runs the programs with both pairs inactive.
 #pragma once
 #ifndef WV_NS
 #error "define WV_NS, WV_PROG, WV_THREADS and WV_FULL before including k_wave.hpp"
 #endif
+#ifndef WV_PACKED
+#define WV_PACKED 0
+#endif
+#include "cyc_pack.hpp"
 #include "launch.hpp"
 #include "pfp.hpp"
 
 namespace WV_NS {
 using namespace hbs;
 
+#if WV_PACKED
+static_assert(WV_THREADS == 64 && !WV_FULL, "the packed form is one wave per check, plain checks only");
+static_assert(WV_PACK >= 1 && WV_PACK <= cycpack::max_pack(), "18 lanes per check in the packed runs");
+constexpr int WV_NPACK = WV_PACK;
+#else
+constexpr int WV_NPACK = 1;
+#endif
+// 1: the final exponentiation's inversions of a workgroup's checks run on lane pairs of one wave
+#ifndef WV_PACK_INV
+#define WV_PACK_INV 1
+#endif
+// 1: outside the packed stages a wave orders its LDS traffic with a wavefront-scope fence instead of
+// the workgroup barrier (it touches only its own region there)
+#ifndef WV_WAVE_SYNC
+#define WV_WAVE_SYNC 0
+#endif
+// 1: the packed stages take turns on the workgroup's waves (stage index modulo WV_PACK) instead of
+// all running on wave 0
+#ifndef WV_PACK_ROTATE
+#define WV_PACK_ROTATE 0
+#endif
+
 constexpr int WV_STRIDE = 36;  // words per slot (2 components x 16, +4 against bank conflicts)
+constexpr int WV_REGION = WV_PROG::WP_NSLOTS * WV_STRIDE;  // words of LDS per check
+
+// lane within the check's wave(s) and the check's wave within the workgroup
+HP_D int wv_lane() { return WV_PACKED ? (int)(threadIdx.x & 63) : (int)threadIdx.x; }
+HP_D int wv_wave() { return WV_PACKED ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0; }
+
+// the barrier between a stage's phases; `group`: the stage moves data between the workgroup's waves
+HP_D void wv_sync(bool group) {
+  if (WV_PACKED && WV_WAVE_SYNC && !group) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
+}
 constexpr int WV_LINE_Q4 = 11;  // k_oct_prep table: 16-byte chunks per (line, lane component)
 constexpr uint32_t WV_ZW[NL] = {0};
 
@@ -378,6 +426,50 @@ HP_D void cyc_run(uint32_t* sm, int lane, uint64_t w0, uint64_t w1) {
   if (holder && rr == 0) st_own(sm, (int)((w1 >> (8 * cyc_pos(role, j))) & 0xFF), h, v);
 }
 
+// cyc_run for the WV_NPACK checks of a workgroup at once, on one wave (cyc_pack.hpp's layout: 18
+// lanes per check, no idle copies); sm0 = region of check 0, check c's slots WV_REGION words further
+// per c.  The same descriptors, role swap and arithmetic per lane as cyc_run; only the lanes differ.
+HP_D void cyc_run_packed(uint32_t* sm0, int lane, uint64_t w0, uint64_t w1) {
+  // the layout arithmetic below depends on the lane alone; computed here, per run, it stays out of the
+  // registers that live across the whole stage loop (hoisted, it spilt five of them)
+  asm volatile("" : "+v"(lane));
+  const int h = cycpack::comp_of(lane), j = cycpack::square_of(lane);
+  const bool active = cycpack::is_active(lane, WV_NPACK), holder = cycpack::is_holder(lane, WV_NPACK);
+  const int row = active ? cycpack::role_of(lane) : 0;
+  uint32_t* sm = sm0 + (active ? cycpack::check_of(lane) : 0) * WV_REGION;
+  const int count = __builtin_amdgcn_readfirstlane((int)((w1 >> 48) & 0xFF));
+  const bool conj = (__builtin_amdgcn_readfirstlane((int)(w1 >> 56)) & 1) != 0;
+  int role = row;
+  Fp v = fp_zero();
+  if (holder) v = ld_own(sm, (int)((w0 >> (8 * cyc_pos(role, j))) & 0xFF), h);
+  // the sources of A, B and A + B are two lanes apart (an idle lane reads lanes it never uses)
+  static_assert(cycpack::source_lane(7, 1, 1) == cycpack::source_lane(7, 0, 1) + 2 &&
+                    cycpack::source_lane(7, 2, 1) == cycpack::source_lane(7, 0, 1) + 4,
+                "cyc_pack.hpp layout");
+  const int la = cycpack::source_lane(lane, 0, WV_NPACK), lb = la + 2, lab = la + 4;
+  const int partner = cycpack::partner_lane(lane, WV_NPACK);
+#pragma unroll 1
+  for (int it = 0; it < count; it++) {
+    const Fp A = shfl_fp(v, la), B = shfl_fp(v, lb);
+    Fp x = fp_addl(A, B);
+    fp_carry1(x);
+    x = fp_sel(j == 2, x, v);
+    const Fp sq = wv_sqr(x);
+    const Fp sA = shfl_fp(sq, la), sB = shfl_fp(sq, lb), sAB = shfl_fp(sq, lab);
+    const Fp L = shfl_fp(v, partner);
+    const bool isX = role != 2 ? j == 0 : j == 1;
+    const bool isZ = role == 2 && j == 0;
+    const Fp u = fp_sub2l(sAB, sA, sB);
+    const Fp T = isX ? h_add_xi_l(sA, sB) : (isZ ? h_xi_l(u) : u);
+    Fp r = fp_red_3k(T, L, isX ? -2 : 2);
+    if (conj && it == count - 1 && (role == 2 ? j == 0 : j == 1)) r = fp_neg(r);
+    v = r;
+    if (row == 1 || row == 2) role = 3 - role;
+  }
+  fp_norm(v);
+  if (holder) st_own(sm, (int)((w1 >> (8 * cyc_pos(role, j))) & 0xFF), h, v);
+}
+
 // the final exponentiation's one inversion (pair 0; both lanes invert the same norm, so the batched
 // variable-time form; k_wave64 also keeps its coefficients unreduced, words.hpp INV_LAZY, which makes
 // the 256-register k_wave spill -- round 6 A/B, profiles/r06/ab_inv.txt)
@@ -416,6 +508,8 @@ HP_D StageDesc load_stage(const uint4* hdr, int st, int pair) {
 HP_D void run_stages(uint32_t* sm, int off, int nst, int h, int pair, bool act0, bool act1, const int4* tl0,
                      const int4* tl1) {
   const uint4* hdr = (const uint4*)WV_PROG::WP_HDR;
+  const int wave = wv_wave();
+  uint32_t* sm0 = sm - wave * WV_REGION;  // packed: the region of the workgroup's first check
   // descriptors are fetched one stage ahead: their L2 latency hides behind the current stage
   StageDesc cur = load_stage(hdr, off, pair);
 #ifdef WV_STAGE_CLOCK  // timing-only builds: core cycles per stage kind (M1 M2 SQ NONE INV CYC), block 0
@@ -441,17 +535,33 @@ HP_D void run_stages(uint32_t* sm, int off, int nst, int h, int pair, bool act0,
 #pragma unroll
     for (int side = 0; side < 2; side++) {
       const uint32_t e = (hd.w >> (16 * side)) & 0xFFFF;
-      if (special == 0 && (e & 1) && pair == side) {
+      // (packed: a check that runs inactive has no table)
+      if (special == 0 && (e & 1) && pair == side && (!WV_PACKED || (side ? tl1 : tl0) != nullptr)) {
         const int4* src = (side ? tl1 : tl0) + ((size_t)((e >> 1) & 0x7F) * 2 + h) * WV_LINE_Q4;
 #pragma unroll
         for (int k = 0; k < WV_LINE_Q4; k++) tline[k] = src[k];
         tslot = (int)(e >> 8);
       }
     }
+    // packed: the stage runs for every check of the workgroup on one wave, between workgroup barriers
+    // (the one that ended the previous stage and the next one, unless those are wave-local)
+    const bool group = WV_PACKED && (special == 2 || (special == 1 && WV_PACK_INV));
+    if (WV_PACKED && WV_WAVE_SYNC && group) __syncthreads();
+    const int owner = WV_PACK_ROTATE ? st % WV_NPACK : 0;  // the wave that runs a packed stage
     if (special == 2) {
-      if (WV_THREADS == 64 || threadIdx.x < 64) cyc_run(sm, 2 * pair + h, cur.p0, cur.p1);  // wave 0's rows
+      if (WV_PACKED) {
+        if (wave == owner) cyc_run_packed(sm0, 2 * pair + h, cur.p0, cur.p1);
+      } else if (WV_THREADS == 64 || threadIdx.x < 64) {
+        cyc_run(sm, 2 * pair + h, cur.p0, cur.p1);  // wave 0's rows
+      }
     } else if (special == 1) {
-      if (pair == 0) {
+      if (WV_PACKED && WV_PACK_INV) {
+        if (wave == owner && pair < WV_NPACK) {  // pair c inverts check c's norm (per-lane code: pairs may diverge)
+          uint32_t* smc = sm0 + pair * WV_REGION;
+          const Fp v = ld_own(smc, hd.w & 0xFF, h);
+          st_own(smc, (hd.w >> 8) & 0xFF, h, wv_inv(v));
+        }
+      } else if (pair == 0) {
         const Fp v = ld_own(sm, hd.w & 0xFF, h);
         st_own(sm, (hd.w >> 8) & 0xFF, h, wv_inv(v));  // pair 0 only: uniform
       }
@@ -471,7 +581,7 @@ HP_D void run_stages(uint32_t* sm, int off, int nst, int h, int pair, bool act0,
 #ifdef WV_STAGE_CLOCK
     tp1 = __builtin_amdgcn_s_memtime();
 #endif
-    __syncthreads();
+    wv_sync(group);
 #ifdef WV_STAGE_CLOCK
     tp2 = __builtin_amdgcn_s_memtime();
 #endif
@@ -496,7 +606,7 @@ HP_D void run_stages(uint32_t* sm, int off, int nst, int h, int pair, bool act0,
 #ifdef WV_STAGE_CLOCK
     tp3 = __builtin_amdgcn_s_memtime();
 #endif
-    __syncthreads();
+    wv_sync(false);
 #ifdef WV_STAGE_CLOCK
     {
       const int sp = (cur.hd.x >> 12) & 0xF, cat = sp == 2 ? 5 : sp == 1 ? 4 : (int)(cur.hd.x & 3);
@@ -634,11 +744,19 @@ HP_D void wave_load12(uint32_t* sm, int h, int pair, int slot, const uint32_t* v
   if (pair < 6) st_own(sm, slot + pair, h, fp_from_words(v + 24 * pair + 12 * h));
 }
 
-__global__ void __launch_bounds__(WV_THREADS, WV_THREADS == 64 ? 2 : 1) k_wave(WaveArgs a) {
-  extern __shared__ uint32_t sm[];
-  const int i = blockIdx.x;
-  if (i >= a.n) return;
-  const int lane = threadIdx.x, h = lane & 1, pair = lane >> 1;
+__global__ void __launch_bounds__(WV_THREADS * WV_NPACK, WV_THREADS == 64 ? 2 : 1) k_wave(WaveArgs a) {
+  extern __shared__ uint32_t smem[];
+  uint32_t* sm = smem + wv_wave() * WV_REGION;  // this check's slots
+  const int i = WV_PACKED ? (int)blockIdx.x * WV_NPACK + wv_wave() : (int)blockIdx.x;
+  if (!WV_PACKED && i >= a.n) return;
+  const int lane = wv_lane(), h = lane & 1, pair = lane >> 1;
+  // packed: a slot past n, or a check with a Q index out of range, stays to the end (it shares the
+  // workgroup's barriers) as a check of two inactive pairs that reads no input
+  bool live = true;
+  if (WV_PACKED) {
+    live = i < a.n;
+    for (int k = 0; k < 2 && live; k++) live = (a.s[k].idx ? a.s[k].idx[i] : (uint32_t)i) < a.s[k].nq;
+  }
   wave_consts(sm, h, pair);
   if (WV_FULL && a.fin) {
     // product mode: F = prod_k fin[i][k] (one MULF program per factor), then the final
@@ -655,12 +773,16 @@ __global__ void __launch_bounds__(WV_THREADS, WV_THREADS == 64 ? 2 : 1) k_wave(W
   } else {
     // the two sides: P (G1) -> XP, YP as Fp2 (x, 0); Q -> QX, QY and T = (Q, 1); activity flags
     bool act0, act1, bad0, bad1;
-    const int4* tl0 = wave_side<0>(a, sm, i, h, pair, act0, bad0);
-    const int4* tl1 = nullptr;
-    act1 = bad1 = false;
-    if (!(a.flags & 16)) tl1 = wave_side<1>(a, sm, i, h, pair, act1, bad1);
+    const int4 *tl0 = nullptr, *tl1 = nullptr;
+    act0 = bad0 = act1 = bad1 = false;
+    if (live) {
+      tl0 = wave_side<0>(a, sm, i, h, pair, act0, bad0);
+      if (!(a.flags & 16)) tl1 = wave_side<1>(a, sm, i, h, pair, act1, bad1);
+    } else {  // every slot above the constants and F holds 0
+      for (int w = (WV_PROG::WP_F + 6) * WV_STRIDE + lane; w < WV_REGION; w += 64) sm[w] = 0;
+    }
     const bool bad = bad0 || bad1;
-    if (bad) {  // index out of range: reject, never read past a table (uniform per workgroup)
+    if (!WV_PACKED && bad) {  // index out of range: reject, never read past a table (uniform per workgroup)
       if (lane == 0 && a.verdict && !a.tree_nw) a.verdict[i] = 0;  // tree mode: the group's stays 0
       return;
     }
@@ -697,7 +819,7 @@ __global__ void __launch_bounds__(WV_THREADS, WV_THREADS == 64 ? 2 : 1) k_wave(W
       if (lane == 0 && a.verdict) a.verdict[g] = all ? 1 : 0;
       return;
     }
-    if (a.flags & 4) {  // Miller only: f (w-basis) out, no final exponentiation
+    if (!WV_PACKED && (a.flags & 4)) {  // Miller only: f (w-basis) out, no final exponentiation
       if (pair < 6 && a.value_out)
         fp_to_words(ld_own(sm, WV_PROG::WP_F + pair, h), a.value_out + (size_t)i * 144 + 24 * pair + 12 * h);
       return;
@@ -708,7 +830,7 @@ __global__ void __launch_bounds__(WV_THREADS, WV_THREADS == 64 ? 2 : 1) k_wave(W
   bool ok = true;
   if (pair < 6) {
     Fp v = ld_own(sm, WV_PROG::WP_E + pair, h);
-    if (a.value_out) {
+    if (a.value_out && live) {
       if ((a.flags & 2) && (pair & 1)) v = fp_neg(v);
       const int pos = (pair & 1) ? 3 + (pair >> 1) : (pair >> 1);
       fp_to_words(v, a.value_out + (size_t)i * 144 + 24 * pos + 12 * h);
@@ -717,7 +839,7 @@ __global__ void __launch_bounds__(WV_THREADS, WV_THREADS == 64 ? 2 : 1) k_wave(W
     ok = fp_is_zero(fp_sub(v, want));
   }
   const bool all = __all(ok);
-  if (lane == 0 && a.verdict) a.verdict[i] = all ? 1 : 0;
+  if (lane == 0 && a.verdict && (!WV_PACKED || i < a.n)) a.verdict[i] = (all && live) ? 1 : 0;
 }
 
 }  // namespace WV_NS

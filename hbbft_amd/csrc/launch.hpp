@@ -80,6 +80,14 @@ constexpr int WAVE_CONJ_VALUE = 2;
 size_t wave64_lds_bytes();
 hipError_t wave64_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,
                          uint8_t* verdict, uint32_t* value_out);
+// The same verdicts / values as wave_verify with wavep_pack() checks per workgroup, one wave each
+// (k_wavep.hip): the cyclotomic-squaring runs and the inversion of a workgroup's checks share one
+// wave's instruction stream.  ceil(n / wavep_pack()) workgroups, wavep_pack() * wave_lds_bytes() of
+// LDS each.  Plain checks only (flags WAVE_NEG_P2 / WAVE_CONJ_VALUE); an index out of range gives
+// verdict 0 and writes no value.
+int wavep_pack();
+hipError_t wavep_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,
+                        uint8_t* verdict, uint32_t* value_out);
 
 // --------------------------------------------------------------- curve / MSM (k_curve.hip)
 // out[i] = k_i * P_i (G1 or G2 ABI words; scalars 8 LE words, any 256-bit integer).

@@ -338,8 +338,11 @@ class Engine:
         HBH_AUTO_OCT_MAX, lane quad up to HBH_AUTO_QUAD_MAX, lane pair above),
         4 = lane pair (two lanes per check, fused), 5 = wave (one 64-lane wave per check: the latency
         kernel), 6 = lane quad (four lanes per check: mid-size batches), 7 = lane octo (eight lanes per
-        check).  0, 1, 2 are retired
-        implementations (HBH_ERR_ARG)."""
+        check), 8 = wave2 (two waves per check: calls of few checks), 10 = wave, packed (one wave
+        per check, two checks per workgroup sharing the cyclotomic-squaring runs and the inversion of
+        the final exponentiation; auto picks it for HBH_AUTO_WAVEP_MIN..HBH_AUTO_WAVEP_MAX = 1,025..1,536
+        checks, ahead of the ladder above).  0, 1, 2 are retired implementations and 9 is not assigned
+        (HBH_ERR_ARG)."""
         check(self._l.hbh_engine_set_pairing_impl(self._h, int(impl)))
 
     def set_ack_impl(self, impl):

@@ -346,6 +346,19 @@ int hbh_fr_poly_eval(size_t npoly, size_t ncoef, const uint8_t* coeffs, size_t n
  *     loop multiplies a step's two lines together beside f^2 and takes their product in one stage,
  *     149 stages per two-pair check instead of WAVE's 210-211.  Latency path for calls of up to
  *     HBH_AUTO_WAVE2_MAX checks (AUTO; plain checks -- the split master check's modes stay on WAVE).
+ *   HBH_IMPL_WAVEP (k_wavep.hip): WAVE's one wave per check and its stage programs, with two
+ *     checks (waves) per workgroup; the final exponentiation's cyclotomic-squaring runs and its
+ *     inversion -- 18 and 2 useful lanes of 64 on WAVE -- run for both checks together on one of the
+ *     workgroup's waves (18 lanes per check, csrc/cyc_pack.hpp), the waves taking turns: 492 k VALU
+ *     instructions per check against WAVE's 648 k.  Plain checks only, like WAVE2.  AUTO uses it for
+ *     calls of HBH_AUTO_WAVEP_MIN..HBH_AUTO_WAVEP_MAX checks, ahead of the ladder below (MIN > MAX
+ *     would mean never).  The range is the run of swept sizes at which its median kernel time is
+ *     below WAVE's and OCT's by more than both cells' min-max spread (profiles/r08/wavep_sweep.json,
+ *     wavep_refine.json, wavep_refine_auto.json, README.md there): 1,025..1,536 checks, where WAVE
+ *     needs a second wave on some SIMDs and WAVEP still runs one round of workgroups -- 2.46-2.48 ms
+ *     against 2.64-2.78 (-6 to -11 %).  Outside it the form does not win: 1,024 checks 2.48 against
+ *     1.80, 2,048 checks 2.59 against 2.71 and 4,096 checks 4.98 against 5.08 (both inside the
+ *     spread), OCT from 4,160 on.
  *   HBH_IMPL_AUTO (the default): WAVE2 up to HBH_AUTO_WAVE2_MAX checks per call, WAVE up to
  *     HBH_AUTO_WAVE_MAX checks per call, OCT up to
  *     HBH_AUTO_OCT_MAX, QUAD up to HBH_AUTO_QUAD_MAX (each one wave per SIMD at its maximum), PAIR
@@ -370,6 +383,9 @@ int hbh_fr_poly_eval(size_t npoly, size_t ncoef, const uint8_t* coeffs, size_t n
 #define HBH_IMPL_QUAD 6
 #define HBH_IMPL_OCT 7
 #define HBH_IMPL_WAVE2 8
+#define HBH_IMPL_WAVEP 10  /* 9 is not assigned */
+#define HBH_AUTO_WAVEP_MIN 1025  /* AUTO: WAVEP for MIN <= checks <= MAX, before the ladder below (MIN 1 / MAX 0: never) */
+#define HBH_AUTO_WAVEP_MAX 1536
 #define HBH_AUTO_WAVE2_MAX 512  /* AUTO: WAVE2 up to here (two waves per check), then WAVE (profiles/r06/latency_c6.txt) */
 #define HBH_AUTO_WAVE_MAX 4096
 #define HBH_AUTO_OCT_MAX 8192
