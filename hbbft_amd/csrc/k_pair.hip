@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256, 2) k_pair_verify(PairArgs a) {
   if (i >= a.n) return;  // both lanes of a pair leave together
   constexpr bool G1 = GEN == 1, G2 = GEN == 2;
   const bool neg2 = (a.flags & 1) != 0;
-  SideState A, B;
+  SideStateH A, B;  // a WALK side's T is homogeneous (pfp.hpp h_dbl_step_h / h_add_step_h)
   const bool ok1 = side_init<W1, G1>(a.s1, i, false, A);
   const bool ok2 = side_init<W2, G2>(a.s2, i, neg2, B);
   if (!ok1 || !ok2) {  // index out of range: reject, never read past a table

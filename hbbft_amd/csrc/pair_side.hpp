@@ -73,22 +73,29 @@ struct PairSide {
 // keeps no P in registers -- the line evaluation multiplies by constants -- and a walked side keeps
 // only T: Q itself is re-read from memory at the 5 addition steps instead of living in 28 VGPRs
 // through the 63 doublings.
-struct SideState {
+//
+// PT: the coordinates T walks in -- HJac for the lane-quad and lane-octo kernels (h_*_step_q / _o),
+// HProj for the lane-pair kernel (h_*_step_h)
+template <class PT>
+struct SideStateT {
   Fp xP, yP;      // P (Montgomery), both lanes (unused when GEN)
   bool act;       // pair contributes (P != O and Q != O)
   bool qinf;      // WALK: Q is the point at infinity (the walk runs from (1, 1), masked out)
   uint32_t q;     // Q index
-  HJac T;         // WALK: the running multiple of Q (own components)
+  PT T;           // WALK: the running multiple of Q (own components)
 };
+using SideState = SideStateT<HJac>;
+using SideStateH = SideStateT<HProj>;
 
-template <bool GEN>
-HP_D Fp side_xP(const SideState& st) { return GEN ? fp_const(hb::G1X_M) : st.xP; }
-template <bool GEN>
-HP_D Fp side_yP(const SideState& st, bool negate) {
+template <bool GEN, class ST>
+HP_D Fp side_xP(const ST& st) { return GEN ? fp_const(hb::G1X_M) : st.xP; }
+template <bool GEN, class ST>
+HP_D Fp side_yP(const ST& st, bool negate) {
   return GEN ? (negate ? fp_neg(fp_const(hb::G1Y_M)) : fp_const(hb::G1Y_M)) : st.yP;
 }
 
-HP_D void side_q(const PairSide& s, const SideState& st, Fp& xQ, Fp& yQ) {
+template <class ST>
+HP_D void side_q(const PairSide& s, const ST& st, Fp& xQ, Fp& yQ) {
   h_g2_load(s.q + (size_t)st.q * 48, xQ, yQ);
   if (st.qinf) {
     xQ = h_one();
@@ -96,8 +103,8 @@ HP_D void side_q(const PairSide& s, const SideState& st, Fp& xQ, Fp& yQ) {
   }
 }
 
-template <bool WALK, bool GEN>
-HP_D bool side_init(const PairSide& s, int i, bool negate, SideState& st) {
+template <bool WALK, bool GEN, class ST>
+HP_D bool side_init(const PairSide& s, int i, bool negate, ST& st) {
   st.q = s.idx ? s.idx[i] : (uint32_t)i;
   if (st.q >= s.nq) return false;
   bool pinf;
@@ -119,7 +126,7 @@ HP_D bool side_init(const PairSide& s, int i, bool negate, SideState& st) {
     st.qinf = lp_both(words_zero(w + (lp_even() ? 0 : 12), 12) && words_zero(w + (lp_even() ? 24 : 36), 12));
     Fp xQ, yQ;
     side_q(s, st, xQ, yQ);  // dummy walk from (1, 1) when Q = O: the pair is masked out
-    st.T = {xQ, yQ, h_one()};
+    st.T = {xQ, yQ, h_one()};  // Z = 1 in Jacobian and in homogeneous coordinates alike
   } else {
     st.qinf = s.qinf[st.q] != 0;
   }
@@ -128,17 +135,18 @@ HP_D bool side_init(const PairSide& s, int i, bool negate, SideState& st) {
 }
 
 // the side's line of this step, evaluated at P: (c0, c1 xP, c4 yP), or 1 for an inactive pair
-// QUAD: the lane-quad variants (qfp.hpp) of the walk and of the evaluation at P
-template <bool WALK, bool GEN, bool DBL, bool QUAD = false>
-HP_D HLine side_line(const PairSide& s, SideState& st, int step, bool negate) {
+// QUAD: the lane-quad variants (qfp.hpp) of the walk (Jacobian T) and of the evaluation at P;
+// otherwise the lane pair's homogeneous walk (pfp.hpp h_dbl_step_h / h_add_step_h)
+template <bool WALK, bool GEN, bool DBL, bool QUAD = false, class ST>
+HP_D HLine side_line(const PairSide& s, ST& st, int step, bool negate) {
   HLine l;
-  if (WALK) {
-    if (DBL) {
-      if constexpr (QUAD) l = h_dbl_step_q(st.T); else l = h_dbl_step(st.T);
+  if constexpr (WALK) {
+    if constexpr (DBL) {
+      if constexpr (QUAD) l = h_dbl_step_q(st.T); else l = h_dbl_step_h(st.T);
     } else {
       Fp xQ, yQ;
       side_q(s, st, xQ, yQ);
-      if constexpr (QUAD) l = h_add_step_q(st.T, xQ, yQ); else l = h_add_step(st.T, xQ, yQ);
+      if constexpr (QUAD) l = h_add_step_q(st.T, xQ, yQ); else l = h_add_step_h(st.T, xQ, yQ);
     }
   } else {
     const int4* p = s.lines + ((size_t)(st.q * PAIR_STEPS + step) * 2 + (lp_even() ? 0 : 1)) * PL_Q4;

@@ -432,6 +432,84 @@ HP_D HLine h_add_step(HJac& T, const Fp& xQ, const Fp& yQ) {
   return l;
 }
 
+// ---------------------------------------------------------------- G2 walk, homogeneous coordinates
+// T = (X : Y : Z) with x = X / Z, y = Y / Z on the twist y^2 = x^3 + b', b' = 4 xi (Costello-Lange-
+// Naehrig's a = 0 formulas, scaled by 4 to clear the halves; tools/gen_wave_prog.py miller1 states
+// the same walk for the wave kernels, there with 12 xi Z carried along, which a sequential lane pair
+// does not need).  The lines are h_dbl_step's / h_add_step's times a nonzero Fp2 factor (a power of
+// the Jacobian Z), which the final exponentiation removes.  No formula inverts, so the dummy walk of
+// a masked pair from (1 : 1 : 1) is harmless.
+//
+// Bounds.  T's coordinates enter and leave every step normalised with |.| < 2p (fp_reduce's (R), or
+// an h_mul output, < 1.26p whenever both operands are < 8p: 1.25p + 64 p^2 2^-392 and p 2^-392 <
+// 2^-10).  h_sqr gives (-p/8, 9p/8) for |a| < 16p.  Every h_mul / h_sqr / fp_mul operand below is
+// normalised, or lazy with |limb| <= 2^29, and stays under 8p; the sums are bounded line by line.
+struct HProj { Fp x, y, z; };
+
+// 6 lane-pair squares + 3 lane-pair products = 6 x 392 + 3 x 588 = 4,116 MADs per lane (the Jacobian
+// h_dbl_step: 7 squares + 4 products = 5,096).
+//   E = 3 b' Z^2 = 12 xi Z^2;  line (Y^2 - E, -3 X^2, 2 Y Z)
+//   X3 = 2 X Y (Y^2 - 3E),  Y3 = (Y^2 + 3E)^2 - 12 E^2,  Z3 = 4 Y^2 (2 Y Z)
+HP_D HLine h_dbl_step_h(HProj& T) {
+  // Z's and Y's squares first, X's uses last: 0.1 ms per 65,536 checks faster than starting with
+  // X Y (fewer spills in the sign instantiation, profiles/r09/README.md)
+  const Fp C = h_sqr(T.z);  // (-p/8, 9p/8)
+  const Fp YZ = h_sqr(fp_add(T.y, T.z));  // (Y + Z) < 4p
+  const Fp B = h_sqr(T.y);  // (-p/8, 9p/8)
+  // H = (Y + Z)^2 - B - C = 2 Y Z: |H| < 3.4p, normalised by the two fp_sub
+  const Fp H = fp_sub(fp_sub(YZ, B), C);
+  // 12 xi C in one carry pass: h_xi_l's limbs are < 2^29 and its value < 2.25p, so 12 times it is
+  // < 27p with int64 terms < 2^33 -- inside fp_red_mk's quotient estimate (top limb < 2^23).
+  // |E| < 1.01p, normalised.
+  const Fp E = fp_red_mk<12, 0>(h_xi_l(C), C);
+  const Fp A = h_mul(T.x, T.y);  // < 1.26p
+  const Fp S = h_sqr(T.x);
+  HLine l;
+  l.c0 = fp_red_mk<1, -1>(B, E);  // B - E, < 2.2p before the pass, reduced
+  l.c1 = fp_lin(-3, S, 0, S);     // |.| < 3.4p, normalised: an fp_mul operand
+  l.c4 = H;
+  const Fp Bm = fp_lin(1, B, -3, E);  // B - 3E, |.| < 4.2p
+  const Fp Bp = fp_lin(1, B, 3, E);   // B + 3E, |.| < 4.2p
+  // X3 = (2A)(B - 3E): 2A is lazy (|limb| < 2^29), |2A| < 2.6p; the product is < 1.26p
+  T.x = h_mul(fp_addl(A, A), Bm);
+  // Y3 = Bp^2 - 12 E^2: 9p/8 + 12 x 9p/8 < 14.7p, int64 terms < 2^32; reduced in one pass
+  const Fp EE = h_sqr(E);
+  T.y = fp_red_mk<1, -12>(h_sqr(Bp), EE);
+  // Z3 = 2 ((2B) H): the product is < 1.26p, doubled inside the carry pass
+  const Fp BH = h_mul(fp_addl(B, B), H);
+  T.z = fp_red_mk<2, 0>(BH, BH);
+  return l;
+}
+
+// Mixed addition T += Q, Q affine: 2 squares + 11 products = 2 x 392 + 11 x 588 = 7,252 MADs per lane.
+// The Jacobian h_add_step is 3 squares + 10 products = 7,056, but it needs T in Jacobian form, and
+// the conversion (X Z : Y Z^2 : Z) costs a square and two products more than the 196 MADs it saves;
+// there are 5 addition steps against 63 doublings.
+//   theta = Y - yQ Z, lambda = X - xQ Z;  line (theta xQ - lambda yQ, -theta, lambda)
+//   G = X lambda^2, H = lambda^3 + Z theta^2 - 2G
+//   X3 = lambda H,  Y3 = theta (G - H) - Y lambda^3,  Z3 = Z lambda^3
+// xQ, yQ are fp_from_words outputs (or 1): (-p/8, 9p/8).
+HP_D HLine h_add_step_h(HProj& T, const Fp& xQ, const Fp& yQ) {
+  const Fp th = fp_sub(T.y, h_mul(yQ, T.z));  // |.| < 3.3p
+  const Fp la = fp_sub(T.x, h_mul(xQ, T.z));  // |.| < 3.3p
+  HLine l;
+  l.c0 = fp_reduce(fp_sub(h_mul(th, xQ), h_mul(la, yQ)));  // < 2.6p before the pass
+  l.c1 = fp_neg(th);
+  l.c4 = la;
+  const Fp C = h_sqr(th);
+  const Fp D = h_sqr(la);
+  const Fp E = h_mul(la, D);   // lambda^3, < 1.26p
+  const Fp F = h_mul(T.z, C);  // < 1.26p
+  const Fp G = h_mul(T.x, D);  // < 1.26p
+  const Fp H = fp_lin(1, fp_addl(E, F), -2, G);  // limbs < 2^30 before the pass; |H| < 5.1p
+  const Fp X3 = h_mul(la, H);                    // < 1.26p
+  // theta (G - H) - E Y: (G - H) < 6.4p; the difference of the two products is < 2.6p
+  T.y = fp_reduce(fp_sub(h_mul(th, fp_sub(G, H)), h_mul(E, T.y)));
+  T.z = h_mul(T.z, E);  // < 1.26p
+  T.x = X3;
+  return l;
+}
+
 // ---------------------------------------------------------------- boundary formats
 // own component of an ABI G2 coordinate pair (x.c0 x.c1 y.c0 y.c1, 12 words each)
 HP_D void h_g2_load(const uint32_t* __restrict__ w, Fp& x, Fp& y) {
