@@ -21,21 +21,128 @@
 namespace hbs {
 
 // ---------------------------------------------------------------- final exponentiation
-// f^|x| (|x| + 1 if PLUS1) for f in the cyclotomic subgroup, square-and-multiply from the top
-template <bool PLUS1>
-HP_D H12 h_exp_abs_x(const H12& base) {
-  const uint64_t e = PLUS1 ? hb::X_ABS + 1 : hb::X_ABS;
-  H12 r = base;
+// f^|x| (|x| + 1 if PLUS1) for f in the cyclotomic subgroup.
+//
+// |x| has six set bits (63, 62, 60, 57, 48, 16), so f^|x| is a product of powers f^(2^k).  The
+// squarings run bottom-up in Karabina's compressed form (pfp.hpp hc_sqr: six lane-pair squares
+// instead of Granger-Scott's nine) up to bit EXP_TOP = 57; the compressed value is parked in per-lane
+// private memory as it passes a set bit (16, 48, 57), so the squaring loop holds four coefficients
+// and nothing else.  The parked powers are then decompressed with ONE Fp2 inversion (Montgomery's
+// simultaneous inversion of the denominators 4 a1: prefix products, h_inv_vartime,
+// back-substitution).  The four set bits from 57 up are close together: t = f^(2^57) is raised to
+// |x| >> 57 = 105 with six Granger-Scott squarings and three products (h_exp_high), which costs less
+// than decompressing three more powers (measured: EXP_TOP = 57 against 60 and 63,
+// profiles/r10/README.md).  f^|x| = t^105 f^(2^48) f^(2^16).
+//
+// The compressed form needs every parked a1 != 0.  The product of the denominators tells (one zero
+// test); then the exponentiation runs the Granger-Scott square-and-multiply loop instead (h_exp_gs).
+// Real inputs take that path: a pair at infinity gives f = 1, which compresses to four zeros.
+constexpr int EXP_TOP = 57;                          // the last compressed squaring
+constexpr uint64_t EXP_HIGH = hb::X_ABS >> EXP_TOP;  // |x| = EXP_HIGH 2^EXP_TOP + the bits below
+constexpr int EXP_HIGH_BITS = 64 - EXP_TOP;
+constexpr int EXP_NPARK = __builtin_popcountll(hb::X_ABS) - __builtin_popcountll(EXP_HIGH) + 1;
+static_assert((hb::X_ABS & 1) == 0 && (hb::X_ABS >> 63) == 1 && (EXP_HIGH & 1) == 1 && EXP_NPARK >= 1,
+              "the base is no factor of f^|x|, and the power at bit EXP_TOP is the last one parked");
+struct ExpPark {
+  int32_t c[EXP_NPARK][4][NL];   // the compressed powers at |x|'s set bits up to EXP_TOP, lowest first
+  int32_t base[6][NL];           // f itself: the PLUS1 factor and the fallback's operand
+  int32_t pre[EXP_NPARK][NL];    // prefix products of the denominators
+};
+
+HP_D void park_fp(int32_t (&d)[NL], const Fp& a) {
+#pragma unroll
+  for (int i = 0; i < NL; i++) d[i] = a.l[i];
+}
+HP_D Fp unpark_fp(const int32_t (&s)[NL]) {
+  Fp r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.l[i] = s[i];
+  return r;
+}
+HP_D H12 unpark12(const int32_t (&s)[6][NL]) {
+  return {{unpark_fp(s[0]), unpark_fp(s[1]), unpark_fp(s[2])}, {unpark_fp(s[3]), unpark_fp(s[4]), unpark_fp(s[5])}};
+}
+
+// the cold path: square-and-multiply from the top with Granger-Scott squarings
+static __device__ __noinline__ void h_exp_gs(const ExpPark& pk, bool plus1, H12& out) {
+  const uint64_t e = hb::X_ABS + (plus1 ? 1 : 0);
+  H12 r = unpark12(pk.base);
 #pragma unroll 1
   for (int k = 62; k >= 0; k--) {
     r = h12_cyclo_sqr(r);
-    if ((e >> k) & 1) r = h12_mul(r, base);
+    if ((e >> k) & 1) r = h12_mul(r, unpark12(pk.base));
+  }
+  out = r;
+}
+
+// t^EXP_HIGH, square-and-multiply from the top with Granger-Scott squarings
+HP_D H12 h_exp_high(const H12& t) {
+  H12 r = t;
+#pragma unroll 1
+  for (int k = EXP_HIGH_BITS - 2; k >= 0; k--) {
+    r = h12_cyclo_sqr(r);
+    if ((EXP_HIGH >> k) & 1) r = h12_mul(r, t);
   }
   return r;
 }
+
+// decompress the parked powers with one shared inversion, raise the highest to EXP_HIGH and
+// multiply them (and f if plus1); false, with out untouched, if a denominator is zero.  Not inlined:
+// the register allocator sees a call boundary, as at the products, and there is one copy for the
+// five exponentiations.
+static __device__ __noinline__ bool h_exp_tail(ExpPark& pk, bool plus1, H12& out) {
+  Fp P;
+#pragma unroll 1
+  for (int j = 0; j < EXP_NPARK; j++) {
+    const Fp d = hc_denom(unpark_fp(pk.c[j][0]));
+    if (j == 0) P = d; else P = h_mul(P, d);
+    park_fp(pk.pre[j], P);
+  }
+  if (h_is_zero(P)) return false;  // the same on both lanes of the pair (lp_both)
+  Fp I = fp_reduce(h_inv_vartime(P));
+  H12 acc;
+#pragma unroll 1
+  for (int j = EXP_NPARK - 1; j >= (plus1 ? -1 : 0); j--) {
+    H12 E;
+    if (j >= 0) {
+      const HC c = {unpark_fp(pk.c[j][0]), unpark_fp(pk.c[j][1]), unpark_fp(pk.c[j][2]), unpark_fp(pk.c[j][3])};
+      Fp di = I;
+      if (j > 0) {
+        di = h_mul(I, unpark_fp(pk.pre[j - 1]));
+        I = h_mul(I, hc_denom(c.a1));
+      }
+      E = hc_decompress(c, di);
+    } else {
+      E = unpark12(pk.base);
+    }
+    if (j == EXP_NPARK - 1) acc = h_exp_high(E); else acc = h12_mul(acc, E);
+  }
+  out = acc;
+  return true;
+}
+
+template <bool PLUS1>
+HP_D H12 h_exp_abs_x(const H12& base, ExpPark& pk) {
+  park_fp(pk.base[0], base.c0.c0); park_fp(pk.base[1], base.c0.c1); park_fp(pk.base[2], base.c0.c2);
+  park_fp(pk.base[3], base.c1.c0); park_fp(pk.base[4], base.c1.c1); park_fp(pk.base[5], base.c1.c2);
+  HC c = hc_compress(base);
+  int slot = 0;
+#pragma unroll 1
+  for (int k = 1; k <= EXP_TOP; k++) {
+    c = hc_sqr(c);
+    if ((hb::X_ABS >> k) & 1) {  // EXP_NPARK times
+      park_fp(pk.c[slot][0], c.a1); park_fp(pk.c[slot][1], c.a2);
+      park_fp(pk.c[slot][2], c.a4); park_fp(pk.c[slot][3], c.a5);
+      slot++;
+    }
+  }
+  H12 r;
+  if (!h_exp_tail(pk, PLUS1, r)) h_exp_gs(pk, PLUS1, r);
+  return r;
+}
 // f^x = conj(f^|x|), f^(x-1) = conj(f^(|x|+1))  (x < 0)
-HP_D H12 h_exp_x(const H12& f) { return h12_conj(h_exp_abs_x<false>(f)); }
-HP_D H12 h_exp_xm1(const H12& f) { return h12_conj(h_exp_abs_x<true>(f)); }
+HP_D H12 h_exp_x(const H12& f, ExpPark& pk) { return h12_conj(h_exp_abs_x<false>(f, pk)); }
+HP_D H12 h_exp_xm1(const H12& f, ExpPark& pk) { return h12_conj(h_exp_abs_x<true>(f, pk)); }
 
 // e = f^(3 (p^12 - 1) / r), pairing 0.14's hard-part chain (x3) reordered so that at most one
 // Fp12 has to outlive an exponentiation (it waits in the LDS stash):
@@ -45,14 +152,15 @@ HP_D H12 h_final_exp(const H12& f, uint32_t* __restrict__ stash) {
   const H12 f1 = h12_mul(h12_conj(f), h12_inv(f));
   const H12 g = h12_mul(h12_frob2(f1), f1);
   stash12(stash, g);
-  H12 a = h_exp_xm1(h_exp_xm1(g));
-  const H12 b = h12_mul(h_exp_x(a), h12_frob1(a));
+  ExpPark pk;  // one parking area for the five exponentiations
+  H12 a = h_exp_xm1(h_exp_xm1(g, pk), pk);
+  const H12 b = h12_mul(h_exp_x(a, pk), h12_frob1(a));
   {
     const H12 gs = unstash12(stash);
     const H12 w = h12_mul(h12_mul(h12_frob2(b), h12_conj(b)), h12_mul(h12_cyclo_sqr(gs), gs));
     stash12(stash, w);
   }
-  const H12 c = h_exp_x(h_exp_x(b));
+  const H12 c = h_exp_x(h_exp_x(b, pk), pk);
   return h12_mul(c, unstash12(stash));
 }
 

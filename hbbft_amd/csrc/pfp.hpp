@@ -373,6 +373,50 @@ HP_D H12 h12_cyclo_sqr(const H12& f) {
   return r;
 }
 
+// ---------------------------------------------------------------- compressed cyclotomic squaring
+// Karabina's compressed form of a cyclotomic element keeps four of the six coefficients of
+// sum a_k w^k: (a1, a2, a4, a5).  It is closed under squaring -- the new (a1, a2, a4, a5) are exactly
+// the second and third blocks of h12_cyclo_sqr, which never read a0 or a3 -- so a chain of squarings
+// costs six lane-pair squares each instead of nine.  a0 and a3 come back from
+//   a3 = (xi a5^2 + 3 a2^2 - 2 a4) / (4 a1),  a0 = (2 a3^2 + a1 a5 - 3 a4 a2) xi + 1,
+// valid whenever a1 != 0 (hc_decompress takes 1 / (4 a1) from the caller, who shares one inversion
+// among several elements).  a1 = 0 happens for real inputs: 1 compresses to four zeros.
+struct HC { Fp a1, a2, a4, a5; };
+
+HP_D HC hc_compress(const H12& f) { return {f.c1.c0, f.c0.c1, f.c0.c2, f.c1.c2}; }
+// input reduced, output reduced: h12_cyclo_sqr's formulas, bounds and carry passes
+HP_D HC hc_sqr(const HC& c) {
+  HC r;
+  {
+    const Fp s1 = h_sqr(c.a1), s4 = h_sqr(c.a4), s14 = h_sqr(fp_add(c.a1, c.a4));
+    r.a2 = fp_red_mk<3, -2>(h_add_xi_l(s1, s4), c.a2);
+    r.a5 = fp_red_mk<3, 2>(fp_sub2l(s14, s1, s4), c.a5);
+  }
+  {
+    const Fp s2 = h_sqr(c.a2), s5 = h_sqr(c.a5), s25 = h_sqr(fp_add(c.a2, c.a5));
+    r.a4 = fp_red_mk<3, -2>(h_add_xi_l(s2, s5), c.a4);
+    r.a1 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), fp_sub2l(s25, s2, s5)), c.a1);
+  }
+  return r;
+}
+// the denominator 4 a1 of a3: a1 reduced -> normalised, |.| < 8p (a product operand)
+HP_D Fp hc_denom(const Fp& a1) { return fp_lin(4, a1, 0, a1); }
+// c reduced, di = 1 / (4 a1) normalised and < 2p -> the full element, reduced.  2 squares + 3
+// products.
+HP_D H12 hc_decompress(const HC& c, const Fp& di) {
+  const Fp s5 = h_sqr(c.a5), s2 = h_sqr(c.a2);  // (-p/8, 9p/8)
+  // xi s5 + 3 s2 - 2 a4: limbs < 2^29 + 3 2^28 before the pass, |.| < 2.25p + 3.4p + 4p
+  Fp t = h_xi_l(s5);
+#pragma unroll
+  for (int i = 0; i < NL; i++) t.l[i] += 3 * s2.l[i];
+  const Fp a3 = h_mul(fp_red_mk<1, -2>(t, c.a4), di);  // < 1.26p
+  // 2 a3^2 - 3 a4 a2 normalised (|.| < 6.1p), + a1 a5 lazy (limbs < 2^29, |.| < 7.4p); times xi, plus
+  // 1: limbs < 2^28 + 2 2^29 and |.| < 16p before the one carry pass
+  const Fp u = fp_addl(fp_lin(2, h_sqr(a3), -3, h_mul(c.a4, c.a2)), h_mul(c.a1, c.a5));
+  const Fp a0 = fp_red_l(h_add_xi_l(h_one(), u));
+  return {{a0, c.a2, c.a4}, {c.a1, a3, c.a5}};
+}
+
 HP_D bool h12_is_one(const H12& f) {
   bool ok = fp_is_zero(fp_sub(f.c0.c0, h_one()));
   ok = ok && fp_is_zero(f.c0.c1) && fp_is_zero(f.c0.c2);
