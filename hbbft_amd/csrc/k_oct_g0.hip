@@ -6,15 +6,13 @@ namespace hbl {
 
 hipError_t oct_verify_g0(hipStream_t s, int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags,
                           uint8_t* verdict, uint32_t* value_out) {
-  return oct_launch<0>(s, n, d1, d2, flags, verdict, value_out);
+  return lane_launch<OctKernels, 0>(s, n, d1, d2, flags, verdict, value_out);
 }
 
 hipError_t oct_verify(hipStream_t s, int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags,
                        uint8_t* verdict, uint32_t* value_out) {
   if (n <= 0) return hipSuccess;
-  // a null P on exactly one side selects the generator instantiation; both null keeps the run-time
-  // generator path of side_init (P1 and P2 held in registers)
-  const int gen = (d1.p == nullptr) == (d2.p == nullptr) ? 0 : (d1.p == nullptr ? 1 : 2);
+  const int gen = pair_gen_mode(d1, d2);
   if (gen == 1) return oct_verify_g1(s, n, d1, d2, flags, verdict, value_out);
   if (gen == 2) return oct_verify_g2(s, n, d1, d2, flags, verdict, value_out);
   return oct_verify_g0(s, n, d1, d2, flags, verdict, value_out);

@@ -2,8 +2,8 @@
 //
 // The serial 68-step walk of one shared point (63 doublings + 5 additions of |x|) with the lane-octo
 // doubling and addition steps (ofp.hpp: 3 and 5 rounds of four Fp2 products), eight lanes per point;
-// pair 0 of each octo writes the table (c0, c1, c4 per step and lane component, PL_Q4 16-byte chunks,
-// pair_side.hpp), which every verify kernel reads unchanged.
+// pair 0 of each octo writes the table (pair_side.hpp line_store), which every verify kernel reads
+// unchanged (line_load).
 #include "launch.hpp"
 #include "pair_side.hpp"
 #include "ofp.hpp"
@@ -25,27 +25,14 @@ __global__ void __launch_bounds__(256, 1) k_oct_prep(int n, const uint32_t* __re
   const bool writer = o_idx() == 0;
   if ((threadIdx.x & 7) == 0) qinf[j] = inf ? 1 : 0;
   HJac T{xQ, yQ, h_one()};
-  int4* base = lines + (size_t)j * PAIR_STEPS * 2 * PL_Q4 + (lp_even() ? 0 : PL_Q4);
+  int4* base = lines + line_at((size_t)j * PAIR_STEPS);
   int step = 0;
 #pragma unroll 1
   for (int b = 62; b >= 0; b--) {
 #pragma unroll 1
     for (int add = 0; add < (((hb::X_ABS >> b) & 1) ? 2 : 1); add++) {
       const HLine l = add ? h_add_step_o(T, xQ, yQ) : h_dbl_step_o(T);
-      if (writer) {
-        int32_t o[4 * PL_Q4];
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-          o[k] = l.c0.l[k];
-          o[NL + k] = l.c1.l[k];
-          o[2 * NL + k] = l.c4.l[k];
-        }
-        o[3 * NL] = 0;
-        o[3 * NL + 1] = 0;
-        int4* dst = base + (size_t)step * 2 * PL_Q4;
-#pragma unroll
-        for (int k = 0; k < PL_Q4; k++) dst[k] = make_int4(o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3]);
-      }
+      if (writer) line_store(base + (size_t)step * LINE_Q4, l);
       step++;
     }
   }

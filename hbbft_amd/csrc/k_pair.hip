@@ -5,6 +5,8 @@
 // pairing 0.14's Miller loop and final exponentiation (oracle/c/bls_cpu.c miller_loop /
 // final_exponentiation restate them) on the lane-pair tower of
 // pfp.hpp: TWO lanes per check, so a 65,536-check batch is 2,048 waves = two waves per SIMD.
+// The kernel body and the final-exponentiation chain are pair_side.hpp's (lane_verify, final_exp),
+// shared with the lane-quad and lane-octo kernels; this file has the lane pair's exponentiation by x.
 //
 // Each G2 side is one of
 //   TABLE: Q is shared by many checks (H per document, W / H_uv per ciphertext): its 68 lines are
@@ -15,12 +17,11 @@
 // exponentiation one Fp12 (6 components per lane, packed to 72 words) is parked in LDS:
 // 256 lanes x 288 B = 72 KiB per workgroup, two workgroups per CU.
 #define HS_MULFN static __device__ __noinline__
-#include "launch.hpp"
 #include "pair_side.hpp"
 
 namespace hbs {
 
-// ---------------------------------------------------------------- final exponentiation
+// ---------------------------------------------------------------- exponentiation by x
 // f^|x| (|x| + 1 if PLUS1) for f in the cyclotomic subgroup.
 //
 // |x| has six set bits (63, 62, 60, 57, 48, 16), so f^|x| is a product of powers f^(2^k).  The
@@ -70,7 +71,7 @@ static __device__ __noinline__ void h_exp_gs(const ExpPark& pk, bool plus1, H12&
 #pragma unroll 1
   for (int k = 62; k >= 0; k--) {
     r = h12_cyclo_sqr(r);
-    if ((e >> k) & 1) r = h12_mul(r, unpark12(pk.base));
+    if ((e >> k) & 1) r = h12_mul<LanePair>(r, unpark12(pk.base));
   }
   out = r;
 }
@@ -81,7 +82,7 @@ HP_D H12 h_exp_high(const H12& t) {
 #pragma unroll 1
   for (int k = EXP_HIGH_BITS - 2; k >= 0; k--) {
     r = h12_cyclo_sqr(r);
-    if ((EXP_HIGH >> k) & 1) r = h12_mul(r, t);
+    if ((EXP_HIGH >> k) & 1) r = h12_mul<LanePair>(r, t);
   }
   return r;
 }
@@ -115,7 +116,7 @@ static __device__ __noinline__ bool h_exp_tail(ExpPark& pk, bool plus1, H12& out
     } else {
       E = unpark12(pk.base);
     }
-    if (j == EXP_NPARK - 1) acc = h_exp_high(E); else acc = h12_mul(acc, E);
+    if (j == EXP_NPARK - 1) acc = h_exp_high(E); else acc = h12_mul<LanePair>(acc, E);
   }
   out = acc;
   return true;
@@ -140,128 +141,39 @@ HP_D H12 h_exp_abs_x(const H12& base, ExpPark& pk) {
   if (!h_exp_tail(pk, PLUS1, r)) h_exp_gs(pk, PLUS1, r);
   return r;
 }
-// f^x = conj(f^|x|), f^(x-1) = conj(f^(|x|+1))  (x < 0)
-HP_D H12 h_exp_x(const H12& f, ExpPark& pk) { return h12_conj(h_exp_abs_x<false>(f, pk)); }
-HP_D H12 h_exp_xm1(const H12& f, ExpPark& pk) { return h12_conj(h_exp_abs_x<true>(f, pk)); }
-
-// e = f^(3 (p^12 - 1) / r), pairing 0.14's hard-part chain (x3) reordered so that at most one
-// Fp12 has to outlive an exponentiation (it waits in the LDS stash):
-//   g = f^((p^6 - 1)(p^2 + 1));  a = (g^(x-1))^(x-1);  b = a^x frob1(a);
-//   w = frob2(b) conj(b) g^3;    e = (b^x)^x w
-HP_D H12 h_final_exp(const H12& f, uint32_t* __restrict__ stash) {
-  const H12 f1 = h12_mul(h12_conj(f), h12_inv(f));
-  const H12 g = h12_mul(h12_frob2(f1), f1);
-  stash12(stash, g);
-  ExpPark pk;  // one parking area for the five exponentiations
-  H12 a = h_exp_xm1(h_exp_xm1(g, pk), pk);
-  const H12 b = h12_mul(h_exp_x(a, pk), h12_frob1(a));
-  {
-    const H12 gs = unstash12(stash);
-    const H12 w = h12_mul(h12_mul(h12_frob2(b), h12_conj(b)), h12_mul(h12_cyclo_sqr(gs), gs));
-    stash12(stash, w);
-  }
-  const H12 c = h_exp_x(h_exp_x(b, pk), pk);
-  return h12_mul(c, unstash12(stash));
-}
+// the lane pair's exponentiation by x for final_exp (pair_side.hpp): one parking area for the five
+struct ExpCompressed {
+  ExpPark pk;
+  HP_D H12 x(const H12& f) { return h12_conj(h_exp_abs_x<false>(f, pk)); }
+  HP_D H12 xm1(const H12& f) { return h12_conj(h_exp_abs_x<true>(f, pk)); }
+};
 
 // GEN: 0 = both P read per check, 1 = P1 is the generator, 2 = P2 is the generator
 template <bool W1, bool W2, int GEN>
 __global__ void __launch_bounds__(256, 2) k_pair_verify(PairArgs a) {
   extern __shared__ uint32_t stash_lds[];
-  const int i = (int)((blockIdx.x * 256u + threadIdx.x) >> 1);
-  if (i >= a.n) return;  // both lanes of a pair leave together
-  constexpr bool G1 = GEN == 1, G2 = GEN == 2;
-  const bool neg2 = (a.flags & 1) != 0;
-  SideStateH A, B;  // a WALK side's T is homogeneous (pfp.hpp h_dbl_step_h / h_add_step_h)
-  const bool ok1 = side_init<W1, G1>(a.s1, i, false, A);
-  const bool ok2 = side_init<W2, G2>(a.s2, i, neg2, B);
-  if (!ok1 || !ok2) {  // index out of range: reject, never read past a table
-    if (lp_even() && a.verdict) a.verdict[i] = 0;
-    return;
-  }
-  H12 f = h12_one();
-  int step = 0;
-#pragma unroll 1
-  for (int b = 62; b >= 0; b--) {
-    // the two sides' lines are multiplied together first, then into f (h12_mul_lines)
-    if (b != 62) f = h12_sqr(f);
-    {
-      const HLine la = side_line<W1, G1, true>(a.s1, A, step, false);
-      const HLine lb = side_line<W2, G2, true>(a.s2, B, step, neg2);
-      f = h12_mul_lines(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
-    }
-    step++;
-    if ((hb::X_ABS >> b) & 1) {
-      const HLine la = side_line<W1, G1, false>(a.s1, A, step, false);
-      const HLine lb = side_line<W2, G2, false>(a.s2, B, step, neg2);
-      f = h12_mul_lines(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
-      step++;
-    }
-  }
-  if (a.flags & 2) f = h12_conj(f);
-  const H12 e = h_final_exp(f, stash_lds + threadIdx.x);
-  if (a.value_out) {
-    uint32_t* o = a.value_out + (size_t)i * 144 + (lp_even() ? 0 : 12);
-    fp_to_words(e.c0.c0, o + 0);
-    fp_to_words(e.c0.c1, o + 24);
-    fp_to_words(e.c0.c2, o + 48);
-    fp_to_words(e.c1.c0, o + 72);
-    fp_to_words(e.c1.c1, o + 96);
-    fp_to_words(e.c1.c2, o + 120);
-  }
-  const bool one = h12_is_one(e);
-  if (lp_even() && a.verdict) a.verdict[i] = one ? 1 : 0;
+  lane_verify<LanePair, ExpCompressed, W1, W2, GEN>(a, stash_lds);
 }
 
 }  // namespace hbs
 
 namespace hbl {
 
-size_t pair_table_bytes(size_t nq) { return nq * (size_t)hbs::PAIR_STEPS * 2 * hbs::PL_Q4 * 16; }
+struct PairKernels {
+  static constexpr int LANES = hbs::LanePair::LANES;
+  template <bool W1, bool W2, int GEN>
+  static constexpr auto kernel = hbs::k_pair_verify<W1, W2, GEN>;
+};
+
+size_t pair_table_bytes(size_t nq) { return nq * (size_t)hbs::PAIR_STEPS * hbs::LINE_Q4 * 16; }
 
 hipError_t pair_verify(hipStream_t s, int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags,
                        uint8_t* verdict, uint32_t* value_out) {
   if (n <= 0) return hipSuccess;
-  hbs::PairArgs a;
-  a.n = n;
-  const PairSideDesc* d[2] = {&d1, &d2};
-  hbs::PairSide* o[2] = {&a.s1, &a.s2};
-  for (int k = 0; k < 2; k++) {
-    o[k]->p = (const uint32_t*)d[k]->p;
-    o[k]->q = (const uint32_t*)d[k]->q;
-    o[k]->lines = (const int4*)d[k]->lines;
-    o[k]->qinf = d[k]->qinf;
-    o[k]->idx = d[k]->idx;
-    o[k]->nq = (uint32_t)d[k]->nq;
-  }
-  a.flags = flags;
-  a.verdict = verdict;
-  a.value_out = value_out;
-  const dim3 grid((unsigned)((2 * (size_t)n + 255) / 256)), block(256);
-  const size_t lds = (size_t)hbs::STASH_WORDS * 256 * 4;
-  const bool w1 = d1.lines == nullptr, w2 = d2.lines == nullptr;
-  // a null P on exactly one side selects the generator instantiation; both null keeps the
-  // run-time generator path of side_init (P1 and P2 held in registers)
-  const int gen = (d1.p == nullptr) == (d2.p == nullptr) ? 0 : (d1.p == nullptr ? 1 : 2);
-#define HBS_PAIR_LAUNCH(G)                                                                 \
-  do {                                                                                     \
-    if (w1 && w2)                                                                          \
-      hipLaunchKernelGGL((hbs::k_pair_verify<true, true, G>), grid, block, lds, s, a);     \
-    else if (w1)                                                                           \
-      hipLaunchKernelGGL((hbs::k_pair_verify<true, false, G>), grid, block, lds, s, a);    \
-    else if (w2)                                                                           \
-      hipLaunchKernelGGL((hbs::k_pair_verify<false, true, G>), grid, block, lds, s, a);    \
-    else                                                                                   \
-      hipLaunchKernelGGL((hbs::k_pair_verify<false, false, G>), grid, block, lds, s, a);   \
-  } while (0)
-  if (gen == 1)
-    HBS_PAIR_LAUNCH(1);
-  else if (gen == 2)
-    HBS_PAIR_LAUNCH(2);
-  else
-    HBS_PAIR_LAUNCH(0);
-#undef HBS_PAIR_LAUNCH
-  return hipGetLastError();
+  const int gen = pair_gen_mode(d1, d2);
+  if (gen == 1) return lane_launch<PairKernels, 1>(s, n, d1, d2, flags, verdict, value_out);
+  if (gen == 2) return lane_launch<PairKernels, 2>(s, n, d1, d2, flags, verdict, value_out);
+  return lane_launch<PairKernels, 0>(s, n, d1, d2, flags, verdict, value_out);
 }
 
 }  // namespace hbl

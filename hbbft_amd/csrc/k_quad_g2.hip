@@ -6,7 +6,7 @@ namespace hbl {
 
 hipError_t quad_verify_g2(hipStream_t s, int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags,
                           uint8_t* verdict, uint32_t* value_out) {
-  return quad_launch<2>(s, n, d1, d2, flags, verdict, value_out);
+  return lane_launch<QuadKernels, 2>(s, n, d1, d2, flags, verdict, value_out);
 }
 
 }  // namespace hbl

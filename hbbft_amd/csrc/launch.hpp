@@ -1,5 +1,5 @@
 // Host-side launchers of the HIP kernels.  Each kernel family lives in its own translation unit
-// (k_pair.hip, k_quad.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip) so the Makefile
+// (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip) so the Makefile
 // compiles them in parallel; engine.hip owns the C ABI, device buffers and streams and calls only
 // these functions.  Its host arithmetic and planning live in host_fr.hpp, wire_host.hpp and ack_plan.hpp.
 #pragma once
@@ -12,6 +12,8 @@ namespace hbl {
 constexpr int HBL_DUPLICATE = 5;  // == HBH_ERR_DUPLICATE_ENTRY
 constexpr int HBL_BAD_INDEX = 1;  // == HBH_ERR_ARG
 // --------------------------------------------------------------- lane-pair pairing (k_pair.hip)
+// pair_verify, quad_verify and oct_verify launch one kernel body on 2, 4 and 8 lanes per check
+// (pair_side.hpp lane_verify and lane_launch).
 // One side of a pairing-equality check.  TABLE side: `lines`/`qinf` from oct_prep over the nq
 // shared G2 points, `idx` picks the table per check.  WALK side (lines == nullptr): `q` holds G2
 // points walked inside the Miller loop, `idx` picks the point per check (nullptr = identity).
@@ -32,14 +34,14 @@ hipError_t oct_prep(hipStream_t s, int n, const void* q, void* lines, uint8_t* q
 hipError_t pair_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,
                        uint8_t* verdict, uint32_t* value_out);
 
-// --------------------------------------------------------------- lane-quad pairing (k_quad.hip)
+// --------------------------------------------------------------- lane-quad pairing (k_quad.hpp, k_quad_g0/g1/g2.hip)
 // The same verdicts / values as pair_verify with FOUR lanes per check (two lane pairs splitting
 // each step's independent products): the mid-size batches, one wave per SIMD at 16,384 checks.
 // TABLE sides read oct_prep tables.
 hipError_t quad_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,
                        uint8_t* verdict, uint32_t* value_out);
 
-// --------------------------------------------------------------- lane-octo pairing (k_oct.hpp)
+// --------------------------------------------------------------- lane-octo pairing (k_oct.hpp, k_oct_g0/g1/g2.hip)
 // The same with EIGHT lanes per check (four lane pairs, four products per round): one wave per SIMD
 // at 8,192 checks.
 hipError_t oct_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,

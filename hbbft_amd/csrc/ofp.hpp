@@ -120,43 +120,6 @@ HP_D H6 h6_mul_o(const H6& a, const H6& b) {
           fp_red_l(fp_addl(fp_sub2l(r[1], v0, v2), v1))};
 }
 
-HP_D H12 h12_mul_o(const H12& a, const H12& b) {
-  H6 t0, t1;
-  h6_mul_pair_o(a.c0, b.c0, a.c1, b.c1, t0, t1);
-  return h12_kcomb(t0, t1, h6_mul_o(h6_add(a.c0, a.c1), h6_add(b.c0, b.c1)));
-}
-
-HP_D H12 h12_sqr_o(const H12& a) {
-  H6 t, s;
-  h6_mul_pair_o(a.c0, a.c1, h6_add(a.c0, a.c1), h6_red(h6_add(a.c0, h6_mul_v(a.c1))), t, s);
-  return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
-           fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
-          {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
-}
-
-// f * (la * lb): the six line products in two rounds, then t0 = f0 C0 beside t1 = f1 (0, c11, c12)
-// (three rounds) and s (two)
-HP_D H12 h12_mul_lines_o(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1,
-                         const Fp& b4) {
-  Fp r[4];
-  {
-    const Fp x[4] = {a0, a1, a4, fp_addl(a0, a4)}, y[4] = {b0, b1, b4, fp_add(b0, b4)};
-    h_mul4(x, y, r);
-  }
-  const Fp a0b0 = r[0], a1b1 = r[1], a4b4 = r[2], t04 = r[3];
-  {
-    const Fp x[4] = {fp_addl(a1, a4), fp_addl(a0, a1), a0, a0}, y[4] = {fp_add(b1, b4), fp_add(b0, b1), b0, b0};
-    h_mul4(x, y, r);
-  }
-  const Fp c11 = fp_red_l(fp_sub2l(t04, a0b0, a4b4));
-  const Fp c12 = fp_red_l(fp_sub2l(r[0], a1b1, a4b4));
-  const H6 C0 = {fp_red_l(h_add_xi_l(a0b0, a4b4)), fp_red_l(fp_sub2l(r[1], a0b0, a1b1)), a1b1};
-  H6 t0, t1;
-  h6_mul_pair_o(f.c0, C0, f.c1, {h_zero(), c11, c12}, t0, t1);
-  const H6 s = h6_mul_o(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
-  return h12_kcomb(t0, t1, s);
-}
-
 // Granger-Scott squaring: nine squares in three rounds (the last one square, computed by every pair)
 HP_D H12 h12_cyclo_sqr_o(const H12& f) {
   const Fp& a0 = f.c0.c0; const Fp& a2 = f.c0.c1; const Fp& a4 = f.c0.c2;
@@ -181,16 +144,6 @@ HP_D H12 h12_cyclo_sqr_o(const H12& f) {
   r.c0.c2 = fp_red_mk<3, -2>(h_add_xi_l(s2, s5), a4);
   r.c1.c0 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), fp_sub2l(s25, s2, s5)), a1);
   return r;
-}
-
-HP_D H12 h12_inv_o(const H12& a) {
-  H6 s0, s1;
-  h6_mul_pair_o(a.c0, a.c0, a.c1, a.c1, s0, s1);
-  const H6 t = h6_red(h6_sub(h6_red(s0), h6_red(h6_mul_v(h6_red(s1)))));
-  const H6 ti = h6_red(h6_inv(t));
-  H6 r0, r1;
-  h6_mul_pair_o(a.c0, ti, a.c1, ti, r0, r1);
-  return h12_red({r0, h6_neg(r1)});
 }
 
 HP_D H12 h12_frob1_o(const H12& f) {
@@ -223,7 +176,7 @@ HP_D H12 h12_frob2_o(const H12& f) {
   return o;
 }
 
-// doubling step (h_dbl_step): eleven products in three rounds
+// doubling step (h_dbl_step_q): eleven products in three rounds
 HP_D HLine h_dbl_step_o(HJac& T) {
   Fp r[4];
   {
@@ -255,7 +208,7 @@ HP_D HLine h_dbl_step_o(HJac& T) {
   return l;
 }
 
-// addition step (h_add_step): thirteen products in five rounds
+// addition step (h_add_step_q): thirteen products in five rounds
 HP_D HLine h_add_step_o(HJac& T, const Fp& xQ, const Fp& yQ) {
   Fp r[4];
   {
@@ -293,5 +246,61 @@ HP_D HLine h_add_step_o(HJac& T, const Fp& xQ, const Fp& yQ) {
   T.z = Z3;
   return l;
 }
+
+// ---------------------------------------------------------------- the lane octo as a width policy
+// (pfp.hpp LanePair): four products per round.  A dual Fp6 product is three rounds, a single one two
+// (the second half-used), the six line products two.
+struct LaneOcto {
+  static constexpr int LANES = 8;
+  static HP_D bool leader() { return (threadIdx.x & 7) == 0; }
+  static HP_D bool value_writer() { return o_idx() == 0; }  // pair 0
+  using Walk = HJac;
+  static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_o(T); }
+  static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_o(T, xQ, yQ); }
+
+  static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul_o(a, b); }
+  template <class A1, class B1>
+  static HP_D void mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    h6_mul_pair_o(a0, b0, h6_of(a1), h6_of(b1), r0, r1);
+  }
+  static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
+    h6_mul_pair_o(a0, b0, a1, {h_zero(), c1, c2}, r0, r1);
+  }
+  static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
+                                H6& C0, Fp& c11, Fp& c12) {
+    Fp r[4];
+    {
+      const Fp x[4] = {a0, a1, a4, fp_addl(a0, a4)}, y[4] = {b0, b1, b4, fp_add(b0, b4)};
+      h_mul4(x, y, r);
+    }
+    const Fp a0b0 = r[0], a1b1 = r[1], a4b4 = r[2], t04 = r[3];
+    {
+      const Fp x[4] = {fp_addl(a1, a4), fp_addl(a0, a1), a0, a0}, y[4] = {fp_add(b1, b4), fp_add(b0, b1), b0, b0};
+      h_mul4(x, y, r);
+    }
+    h_line_comb(a0b0, a1b1, a4b4, t04, r[0], r[1], C0, c11, c12);
+  }
+  static HP_D H12 cyclo_sqr(const H12& f) { return h12_cyclo_sqr_o(f); }
+  static HP_D H12 frob1(const H12& f) { return h12_frob1_o(f); }
+  static HP_D H12 frob2(const H12& f) { return h12_frob2_o(f); }
+
+  // both sides' raw lines first, then their evaluation at P in one round of four Fp products
+  template <bool G1, bool G2, class RA, class RB, class ST>
+  static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
+                              HLine& lb) {
+    const HLine ra = raw_a();
+    const HLine rb = raw_b();
+    Fp r[4];
+    const Fp x[4] = {ra.c1, ra.c4, rb.c1, rb.c4};
+    const Fp y[4] = {side_xP<G1>(A), side_yP<G1>(A, false), side_xP<G2>(B), side_yP<G2>(B, neg2)};
+    fp_mul4(x, y, r);
+    la.c0 = A.act ? ra.c0 : h_one();
+    la.c1 = A.act ? r[0] : fp_zero();
+    la.c4 = A.act ? r[1] : fp_zero();
+    lb.c0 = B.act ? rb.c0 : h_one();
+    lb.c1 = B.act ? r[2] : fp_zero();
+    lb.c4 = B.act ? r[3] : fp_zero();
+  }
+};
 
 }  // namespace hbs

@@ -1,6 +1,9 @@
-// Shared by the lane-pair (k_pair.hip) and lane-quad (k_quad.hip) pairing kernels: the LDS stash
-// of the final exponentiation and the Miller-loop sides (line tables, walked G2 points, P).
+// Shared by the lane-pair (k_pair.hip), lane-quad (k_quad.hpp) and lane-octo (k_oct.hpp) pairing
+// kernels: the LDS stash of the final exponentiation, the Miller-loop sides (line tables, walked G2
+// points, P), and the one kernel body, final-exponentiation chain and launcher of the three, each
+// written over a width policy (pfp.hpp LanePair, qfp.hpp LaneQuad, ofp.hpp LaneOcto).
 #pragma once
+#include "launch.hpp"
 #include "qfp.hpp"
 
 namespace hbs {
@@ -69,31 +72,6 @@ struct PairSide {
   uint32_t nq;          // number of Q points / tables
 };
 
-// Register budget (2 waves per SIMD = 256 VGPRs per lane): a side whose P is the generator (GEN)
-// keeps no P in registers -- the line evaluation multiplies by constants -- and a walked side keeps
-// only T: Q itself is re-read from memory at the 5 addition steps instead of living in 28 VGPRs
-// through the 63 doublings.
-//
-// PT: the coordinates T walks in -- HJac for the lane-quad and lane-octo kernels (h_*_step_q / _o),
-// HProj for the lane-pair kernel (h_*_step_h)
-template <class PT>
-struct SideStateT {
-  Fp xP, yP;      // P (Montgomery), both lanes (unused when GEN)
-  bool act;       // pair contributes (P != O and Q != O)
-  bool qinf;      // WALK: Q is the point at infinity (the walk runs from (1, 1), masked out)
-  uint32_t q;     // Q index
-  PT T;           // WALK: the running multiple of Q (own components)
-};
-using SideState = SideStateT<HJac>;
-using SideStateH = SideStateT<HProj>;
-
-template <bool GEN, class ST>
-HP_D Fp side_xP(const ST& st) { return GEN ? fp_const(hb::G1X_M) : st.xP; }
-template <bool GEN, class ST>
-HP_D Fp side_yP(const ST& st, bool negate) {
-  return GEN ? (negate ? fp_neg(fp_const(hb::G1Y_M)) : fp_const(hb::G1Y_M)) : st.yP;
-}
-
 template <class ST>
 HP_D void side_q(const PairSide& s, const ST& st, Fp& xQ, Fp& yQ) {
   h_g2_load(s.q + (size_t)st.q * 48, xQ, yQ);
@@ -134,47 +112,55 @@ HP_D bool side_init(const PairSide& s, int i, bool negate, ST& st) {
   return true;
 }
 
-// the side's line of this step, evaluated at P: (c0, c1 xP, c4 yP), or 1 for an inactive pair
-// QUAD: the lane-quad variants (qfp.hpp) of the walk (Jacobian T) and of the evaluation at P;
-// otherwise the lane pair's homogeneous walk (pfp.hpp h_dbl_step_h / h_add_step_h)
-template <bool WALK, bool GEN, bool DBL, bool QUAD = false, class ST>
-HP_D HLine side_line(const PairSide& s, ST& st, int step, bool negate) {
+// ---------------------------------------------------------------- line tables
+// A table holds, per shared G2 point, the PAIR_STEPS raw lines of its walk.  Entry e = q PAIR_STEPS +
+// step is two runs of PL_Q4 16-byte chunks, one per lane component (even lane first): c0, c1, c4 as
+// 3 x 14 signed limbs and two words of padding.  k_oct_prep writes it, every verify kernel reads it.
+// line_at: the offset in chunks of this lane's run of entry e; line_load / line_store take the run.
+constexpr int LINE_Q4 = 2 * PL_Q4;  // chunks per entry
+HP_D size_t line_at(size_t e) { return e * LINE_Q4 + (lp_even() ? 0 : PL_Q4); }
+HP_D HLine line_load(const int4* __restrict__ p) {
+  int32_t w[4 * PL_Q4];
+#pragma unroll
+  for (int k = 0; k < PL_Q4; k++) {
+    const int4 v = p[k];
+    w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+  }
   HLine l;
-  if constexpr (WALK) {
-    if constexpr (DBL) {
-      if constexpr (QUAD) l = h_dbl_step_q(st.T); else l = h_dbl_step_h(st.T);
-    } else {
-      Fp xQ, yQ;
-      side_q(s, st, xQ, yQ);
-      if constexpr (QUAD) l = h_add_step_q(st.T, xQ, yQ); else l = h_add_step_h(st.T, xQ, yQ);
-    }
-  } else {
-    const int4* p = s.lines + ((size_t)(st.q * PAIR_STEPS + step) * 2 + (lp_even() ? 0 : 1)) * PL_Q4;
-    int32_t w[4 * PL_Q4];
 #pragma unroll
-    for (int k = 0; k < PL_Q4; k++) {
-      const int4 v = p[k];
-      w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
-    }
+  for (int j = 0; j < NL; j++) {
+    l.c0.l[j] = w[j];
+    l.c1.l[j] = w[NL + j];
+    l.c4.l[j] = w[2 * NL + j];
+  }
+  return l;
+}
+HP_D void line_store(int4* __restrict__ p, const HLine& l) {
+  int32_t w[4 * PL_Q4];
 #pragma unroll
-    for (int j = 0; j < NL; j++) {
-      l.c0.l[j] = w[j];
-      l.c1.l[j] = w[NL + j];
-      l.c4.l[j] = w[2 * NL + j];
-    }
+  for (int j = 0; j < NL; j++) {
+    w[j] = l.c0.l[j];
+    w[NL + j] = l.c1.l[j];
+    w[2 * NL + j] = l.c4.l[j];
   }
-  HLine e;
-  e.c0 = st.act ? l.c0 : h_one();
-  if constexpr (QUAD) {
-    Fp c1, c4;
-    fp_mul2(l.c1, side_xP<GEN>(st), l.c4, side_yP<GEN>(st, negate), c1, c4);
-    e.c1 = st.act ? c1 : fp_zero();
-    e.c4 = st.act ? c4 : fp_zero();
+  w[3 * NL] = 0;
+  w[3 * NL + 1] = 0;
+#pragma unroll
+  for (int k = 0; k < PL_Q4; k++) p[k] = make_int4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+
+// a side's raw line of this step: the walk of T (WALK) or the table entry (TABLE)
+template <class G, bool WALK, bool DBL, class ST>
+HP_D HLine side_raw(const PairSide& s, ST& st, int step) {
+  if constexpr (!WALK) {
+    return line_load(s.lines + line_at(st.q * PAIR_STEPS + step));
+  } else if constexpr (DBL) {
+    return G::dbl_step(st.T);
   } else {
-    e.c1 = st.act ? fp_mul(l.c1, side_xP<GEN>(st)) : fp_zero();
-    e.c4 = st.act ? fp_mul(l.c4, side_yP<GEN>(st, negate)) : fp_zero();
+    Fp xQ, yQ;
+    side_q(s, st, xQ, yQ);
+    return G::add_step(st.T, xQ, yQ);
   }
-  return e;
 }
 
 struct PairArgs {
@@ -185,4 +171,155 @@ struct PairArgs {
   uint32_t* value_out;  // 144 canonical words per check (may be null)
 };
 
+
+// ---------------------------------------------------------------- final exponentiation
+// f^|x| (|x| + 1 if PLUS1) for f in the cyclotomic subgroup: square-and-multiply from the top with
+// Granger-Scott squarings
+template <class G, bool PLUS1>
+HP_D H12 exp_abs_x_gs(const H12& base) {
+  const uint64_t e = PLUS1 ? hb::X_ABS + 1 : hb::X_ABS;
+  H12 r = base;
+#pragma unroll 1
+  for (int k = 62; k >= 0; k--) {
+    r = G::cyclo_sqr(r);
+    if ((e >> k) & 1) r = h12_mul<G>(r, base);
+  }
+  return r;
+}
+// How final_exp takes f^x and f^(x-1): x < 0, so f^x = conj(f^|x|), f^(x-1) = conj(f^(|x|+1)).  This
+// one is the plain loop; k_pair.hip has the lane pair's.
+template <class G>
+struct ExpGs {
+  HP_D H12 x(const H12& f) { return h12_conj(exp_abs_x_gs<G, false>(f)); }
+  HP_D H12 xm1(const H12& f) { return h12_conj(exp_abs_x_gs<G, true>(f)); }
+};
+
+// e = f^(3 (p^12 - 1) / r), pairing 0.14's hard-part chain (x3) reordered so that at most one
+// Fp12 has to outlive an exponentiation (it waits in the LDS stash):
+//   g = f^((p^6 - 1)(p^2 + 1));  a = (g^(x-1))^(x-1);  b = a^x frob1(a);
+//   w = frob2(b) conj(b) g^3;    e = (b^x)^x w
+// Exp: the exponentiation by x (ExpGs, or one with state of its own that the five share)
+template <class G, class Exp>
+HP_D H12 final_exp(const H12& f, uint32_t* __restrict__ stash) {
+  const H12 f1 = h12_mul<G>(h12_conj(f), h12_inv<G>(f));
+  const H12 g = h12_mul<G>(G::frob2(f1), f1);
+  stash12(stash, g);
+  Exp ex;
+  H12 a = ex.xm1(ex.xm1(g));
+  const H12 b = h12_mul<G>(ex.x(a), G::frob1(a));
+  {
+    const H12 gs = unstash12(stash);
+    const H12 w = h12_mul<G>(h12_mul<G>(G::frob2(b), h12_conj(b)), h12_mul<G>(G::cyclo_sqr(gs), gs));
+    stash12(stash, w);
+  }
+  const H12 c = ex.x(ex.x(b));
+  return h12_mul<G>(c, unstash12(stash));
+}
+
+// ---------------------------------------------------------------- the pairing-equality check
+// verdict[i] = e(P1_i, Q1_i) == e(P2_i, Q2_i), computed as FE(f_{|x|,Q1}(P1) f_{|x|,Q2}(-P2)) == 1 with
+// one 2-pair multi-Miller loop and one final exponentiation, on G::LANES lanes per check: the body of
+// k_pair_verify, k_quad_verify and k_oct_verify.  W1 / W2: the side WALKs (else TABLE); GEN: 0 = both
+// P read per check, 1 = P1 is the generator, 2 = P2 is the generator.  stash: the workgroup's LDS
+// stash.
+template <class G, class Exp, bool W1, bool W2, int GEN>
+HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
+  const int i = (int)((blockIdx.x * 256u + threadIdx.x) / (unsigned)G::LANES);
+  if (i >= a.n) return;  // the lanes of a check leave together
+  constexpr bool G1 = GEN == 1, G2 = GEN == 2;
+  const bool neg2 = (a.flags & 1) != 0;
+  SideStateT<typename G::Walk> A, B;
+  const bool ok1 = side_init<W1, G1>(a.s1, i, false, A);
+  const bool ok2 = side_init<W2, G2>(a.s2, i, neg2, B);
+  if (!ok1 || !ok2) {  // index out of range: reject, never read past a table
+    if (G::leader() && a.verdict) a.verdict[i] = 0;
+    return;
+  }
+  H12 f = h12_one();
+  int step = 0;
+#pragma unroll 1
+  for (int b = 62; b >= 0; b--) {
+    // the two sides' lines are multiplied together first, then into f (h12_mul_lines)
+    if (b != 62) f = h12_sqr<G>(f);
+    {
+      HLine la, lb;
+      G::template lines_at_p<G1, G2>([&]() HP_L { return side_raw<G, W1, true>(a.s1, A, step); },
+                                     [&]() HP_L { return side_raw<G, W2, true>(a.s2, B, step); }, A, B, neg2, la, lb);
+      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
+    }
+    step++;
+    if ((hb::X_ABS >> b) & 1) {
+      HLine la, lb;
+      G::template lines_at_p<G1, G2>([&]() HP_L { return side_raw<G, W1, false>(a.s1, A, step); },
+                                     [&]() HP_L { return side_raw<G, W2, false>(a.s2, B, step); }, A, B, neg2, la, lb);
+      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
+      step++;
+    }
+  }
+  if (a.flags & 2) f = h12_conj(f);
+  const H12 e = final_exp<G, Exp>(f, stash + threadIdx.x);
+  if (a.value_out && G::value_writer()) {
+    uint32_t* o = a.value_out + (size_t)i * 144 + (lp_even() ? 0 : 12);
+    fp_to_words(e.c0.c0, o + 0);
+    fp_to_words(e.c0.c1, o + 24);
+    fp_to_words(e.c0.c2, o + 48);
+    fp_to_words(e.c1.c0, o + 72);
+    fp_to_words(e.c1.c1, o + 96);
+    fp_to_words(e.c1.c2, o + 120);
+  }
+  const bool one = h12_is_one(e);
+  if (G::leader() && a.verdict) a.verdict[i] = one ? 1 : 0;
+}
+
 }  // namespace hbs
+
+// ---------------------------------------------------------------- launching
+namespace hbl {
+
+inline hbs::PairArgs pair_args(int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags, uint8_t* verdict,
+                               uint32_t* value_out) {
+  hbs::PairArgs a;
+  a.n = n;
+  const PairSideDesc* d[2] = {&d1, &d2};
+  hbs::PairSide* o[2] = {&a.s1, &a.s2};
+  for (int k = 0; k < 2; k++) {
+    o[k]->p = (const uint32_t*)d[k]->p;
+    o[k]->q = (const uint32_t*)d[k]->q;
+    o[k]->lines = (const int4*)d[k]->lines;
+    o[k]->qinf = d[k]->qinf;
+    o[k]->idx = d[k]->idx;
+    o[k]->nq = (uint32_t)d[k]->nq;
+  }
+  a.flags = flags;
+  a.verdict = verdict;
+  a.value_out = value_out;
+  return a;
+}
+
+// a null P on exactly one side selects the generator instantiation (1 or 2); both null keeps the
+// run-time generator path of side_init (P1 and P2 held in registers)
+inline int pair_gen_mode(const PairSideDesc& d1, const PairSideDesc& d2) {
+  return (d1.p == nullptr) == (d2.p == nullptr) ? 0 : (d1.p == nullptr ? 1 : 2);
+}
+
+// launch the WALK / TABLE variant that the two sides ask for, of generator mode GEN.  K names a
+// width's kernels: K::LANES and K::kernel<W1, W2, GEN>.
+template <class K, int GEN>
+hipError_t lane_launch(hipStream_t s, int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags,
+                       uint8_t* verdict, uint32_t* value_out) {
+  const hbs::PairArgs a = pair_args(n, d1, d2, flags, verdict, value_out);
+  const dim3 grid((unsigned)((K::LANES * (size_t)n + 255) / 256)), block(256);
+  const size_t lds = (size_t)hbs::STASH_WORDS * 256 * 4;
+  const bool w1 = d1.lines == nullptr, w2 = d2.lines == nullptr;
+  if (w1 && w2)
+    hipLaunchKernelGGL((K::template kernel<true, true, GEN>), grid, block, lds, s, a);
+  else if (w1)
+    hipLaunchKernelGGL((K::template kernel<true, false, GEN>), grid, block, lds, s, a);
+  else if (w2)
+    hipLaunchKernelGGL((K::template kernel<false, true, GEN>), grid, block, lds, s, a);
+  else
+    hipLaunchKernelGGL((K::template kernel<false, false, GEN>), grid, block, lds, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace hbl

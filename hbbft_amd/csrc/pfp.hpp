@@ -28,6 +28,7 @@
 #include "words.hpp"
 
 #define HP_D __device__ __forceinline__
+#define HP_L __attribute__((always_inline))  // on a lambda
 
 namespace hbs {
 
@@ -228,22 +229,6 @@ HP_D H6 h6_mul(const H6& a, const H6& b) {
   const Fp c2 = fp_red_l(fp_addl(fp_sub2l(h_mul(fp_addl(a.c0, a.c2), fp_add(b.c0, b.c2)), v0, v2), v1));
   return {c0, c1, c2};
 }
-// x (a + b v)
-HP_D H6 h6_mul_01(const H6& x, const Fp& a, const Fp& b) {
-  const Fp t0 = h_mul(x.c0, a);
-  const Fp t1 = h_mul(x.c1, b);
-  const Fp u = h_mul(x.c2, b);
-  const Fp w = h_mul(x.c2, a);
-  const Fp s = h_mul(fp_addl(x.c0, x.c1), fp_add(a, b));
-  return {fp_add(t0, h_mul_xi(u)), fp_sub(fp_subl(s, t0), t1), fp_add(t1, w)};
-}
-// x (b v)
-HP_D H6 h6_mul_1(const H6& x, const Fp& b) {
-  const Fp r0 = h_mul(x.c2, b);
-  const Fp r1 = h_mul(x.c0, b);
-  const Fp r2 = h_mul(x.c1, b);
-  return {h_mul_xi(r0), r1, r2};
-}
 HP_D H6 h6_inv(const H6& a) {
   const Fp c0 = fp_reduce(fp_sub(h_sqr(a.c0), h_mul_xi(h_mul(a.c1, a.c2))));
   const Fp c1 = fp_reduce(fp_sub(h_mul_xi(h_sqr(a.c2)), h_mul(a.c0, a.c1)));
@@ -267,30 +252,6 @@ HP_D H12 h12_kcomb(const H6& t0, const H6& t1, const H6& s) {
            fp_red_l(fp_sub2l(s.c2, t0.c2, t1.c2))}};
 }
 
-// inputs reduced; output reduced
-HP_D H12 h12_mul(const H12& a, const H12& b) {
-  const H6 t0 = h6_mul(a.c0, b.c0);
-  const H6 t1 = h6_mul(a.c1, b.c1);
-  const H6 s = h6_mul(h6_add(a.c0, a.c1), h6_add(b.c0, b.c1));
-  return h12_kcomb(t0, t1, s);
-}
-// complex squaring: t = a0 a1, s = (a0 + a1)(a0 + v a1); c0 = s - t - v t, c1 = 2 t (one pass each)
-HP_D H12 h12_sqr(const H12& a) {
-  const H6 t = h6_mul(a.c0, a.c1);
-  const H6 s = h6_mul(h6_add(a.c0, a.c1), h6_red(h6_add(a.c0, h6_mul_v(a.c1))));
-  return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
-           fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
-          {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
-}
-// f (c0 + c1 w^2 + c4 w^3); c0, c1, c4 normalised, < 2p
-HP_D H12 h12_mul_014(const H12& f, const Fp& c0, const Fp& c1, const Fp& c4) {
-  const H6 fs = h6_add(f.c0, f.c1);
-  const Fp c14 = fp_add(c1, c4);
-  const H6 t0 = h6_red(h6_mul_01(f.c0, c0, c1));
-  const H6 t1 = h6_red(h6_mul_1(f.c1, c4));
-  const H6 s = h6_red(h6_mul_01(fs, c0, c14));
-  return h12_red({h6_add(t0, h6_mul_v(t1)), h6_sub(h6_sub(s, t0), t1)});
-}
 // x (b1 v + b2 v^2): c0 = xi (a1 b2 + a2 b1), c1 = a0 b1 + xi a2 b2, c2 = a0 b2 + a1 b1 (5 products);
 // outputs reduced
 HP_D H6 h6_mul_12(const H6& x, const Fp& b1, const Fp& b2) {
@@ -301,29 +262,62 @@ HP_D H6 h6_mul_12(const H6& x, const Fp& b1, const Fp& b2) {
   const Fp c2 = fp_red_l(fp_addl(h_mul(x.c0, b2), u));
   return {c0, c1, c2};
 }
-// f * (la * lb) for two sparse lines (c0 + c1 w^2 + c4 w^3 each, normalised, < 2p): the line
-// product L = (C0, C1) has C1.c0 = 0 (6 products), then one Karatsuba step with the sparse C1
-// (6 + 5 + 6 products) -- 23 lane-pair products instead of 2 x 13 for two h12_mul_014.
-HP_D H12 h12_mul_lines(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1,
-                       const Fp& b4) {
-  const Fp a0b0 = h_mul(a0, b0);
-  const Fp a1b1 = h_mul(a1, b1);
-  const Fp a4b4 = h_mul(a4, b4);
-  // the line product L = (C0, (0, c11, c12)), each coefficient reduced in one carry pass
-  const Fp c11 = fp_red_l(fp_sub2l(h_mul(fp_addl(a0, a4), fp_add(b0, b4)), a0b0, a4b4));
-  const Fp c12 = fp_red_l(fp_sub2l(h_mul(fp_addl(a1, a4), fp_add(b1, b4)), a1b1, a4b4));
-  const H6 C0 = {fp_red_l(h_add_xi_l(a0b0, a4b4)),
-                 fp_red_l(fp_sub2l(h_mul(fp_addl(a0, a1), fp_add(b0, b1)), a0b0, a1b1)), a1b1};
-  // f L: Karatsuba over Fp6 with the sparse L.c1 (6 + 5 + 6 products); h6_mul / h6_mul_12 reduce
-  const H6 t0 = h6_mul(f.c0, C0);
-  const H6 t1 = h6_mul_12(f.c1, c11, c12);
-  const H6 s = h6_mul(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
+
+// ---------------------------------------------------------------- Fp12 over a lane group
+// The Fp12 operations of the pairing check, written once for the lane pair, the lane quad (qfp.hpp)
+// and the lane octo (ofp.hpp).  G is the width's policy (LanePair below, LaneQuad, LaneOcto): a
+// struct of static functions that says how many independent Fp2 products run side by side.  These
+// use
+//   G::mul6x2(a0, b0, a1, b1, r0, r1)         the dual Fp6 product (a0 b0, a1 b1)
+//   G::mul6x2_12(a0, b0, a1, c1, c2, r0, r1)  the same with b1 = (0, c1, c2)
+//   G::mul6(a, b)                             one Fp6 product
+//   G::line_product(a0 .. b4, C0, c11, c12)   the product (C0, (0, c11, c12)) of two sparse lines
+// An operand of a dual product may be a callable that returns it (h6_of): a width that runs the two
+// products one after the other forms the second one's operands after the first product, so that
+// they are not live across its calls.
+HP_D const H6& h6_of(const H6& a) { return a; }
+template <class F>
+HP_D auto h6_of(const F& f) -> decltype(f()) { return f(); }
+
+// inputs reduced; output reduced
+template <class G>
+HP_D H12 h12_mul(const H12& a, const H12& b) {
+  H6 t0, t1;
+  G::mul6x2(a.c0, b.c0, a.c1, b.c1, t0, t1);
+  const H6 s = G::mul6(h6_add(a.c0, a.c1), h6_add(b.c0, b.c1));
   return h12_kcomb(t0, t1, s);
 }
+// complex squaring: t = a0 a1, s = (a0 + a1)(a0 + v a1); c0 = s - t - v t, c1 = 2 t (one pass each)
+template <class G>
+HP_D H12 h12_sqr(const H12& a) {
+  H6 t, s;
+  G::mul6x2(a.c0, a.c1, [&]() HP_L { return h6_add(a.c0, a.c1); },
+            [&]() HP_L { return h6_red(h6_add(a.c0, h6_mul_v(a.c1))); }, t, s);
+  return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
+           fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
+          {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
+}
+// f * (la * lb) for two sparse lines (c0 + c1 w^2 + c4 w^3 each, normalised, < 2p): the line
+// product L = (C0, C1) has C1.c0 = 0 (6 products), then one Karatsuba step over Fp6 with the sparse
+// C1 -- on the lane pair 6 + 5 + 6 products, 23 in all instead of 2 x 13 for one line at a time.
+template <class G>
+HP_D H12 h12_mul_lines(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1,
+                       const Fp& b4) {
+  H6 C0, t0, t1;
+  Fp c11, c12;
+  G::line_product(a0, a1, a4, b0, b1, b4, C0, c11, c12);
+  G::mul6x2_12(f.c0, C0, f.c1, c11, c12, t0, t1);
+  const H6 s = G::mul6(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
+  return h12_kcomb(t0, t1, s);
+}
+template <class G>
 HP_D H12 h12_inv(const H12& a) {
-  const H6 t = h6_red(h6_sub(h6_red(h6_mul(a.c0, a.c0)), h6_red(h6_mul_v(h6_red(h6_mul(a.c1, a.c1))))));
+  H6 s0, s1, r0, r1;
+  G::mul6x2(a.c0, a.c0, a.c1, a.c1, s0, s1);
+  const H6 t = h6_red(h6_sub(h6_red(s0), h6_red(h6_mul_v(h6_red(s1)))));
   const H6 ti = h6_red(h6_inv(t));
-  return h12_red({h6_mul(a.c0, ti), h6_neg(h6_mul(a.c1, ti))});
+  G::mul6x2(a.c0, ti, a.c1, ti, r0, r1);
+  return h12_red({r0, h6_neg(r1)});
 }
 
 #define HP_FROB1(K) h_const(hb::FROB1_##K##_C0, hb::FROB1_##K##_C1)
@@ -430,59 +424,13 @@ HP_D bool h12_is_one(const H12& f) {
 struct HJac { Fp x, y, z; };
 struct HLine { Fp c0, c1, c4; };
 
-HP_D HLine h_dbl_step(HJac& T) {
-  const Fp A = h_sqr(T.x);
-  const Fp B = h_sqr(T.y);
-  const Fp C = h_sqr(B);
-  const Fp D = fp_lin(2, fp_sub(fp_sub(h_sqr(fp_add(T.x, B)), A), C), 0, C);
-  const Fp E = fp_lin(3, A, 0, A);
-  const Fp ZZ = h_sqr(T.z);
-  HLine l;
-  l.c0 = fp_sub(h_mul(E, T.x), fp_add(B, B));
-  l.c1 = fp_neg(h_mul(E, ZZ));
-  const Fp Z3 = fp_sub(fp_sub(h_sqr(fp_add(T.y, T.z)), B), ZZ);
-  l.c4 = h_mul(Z3, ZZ);
-  const Fp F = h_sqr(E);
-  const Fp X3 = fp_sub(F, fp_add(D, D));
-  T.y = fp_sub(h_mul(E, fp_sub(D, X3)), fp_lin(8, C, 0, C));
-  T.x = X3;
-  T.z = Z3;
-  l.c0 = fp_reduce(l.c0);
-  T.x = fp_reduce(T.x);
-  T.y = fp_reduce(T.y);
-  T.z = fp_reduce(T.z);
-  return l;
-}
-
-HP_D HLine h_add_step(HJac& T, const Fp& xQ, const Fp& yQ) {
-  const Fp Z1Z1 = h_sqr(T.z);
-  const Fp U2 = h_mul(xQ, Z1Z1);
-  const Fp S2 = h_mul(h_mul(yQ, T.z), Z1Z1);
-  const Fp H = fp_sub(U2, T.x);
-  const Fp r = fp_sub(S2, T.y);
-  const Fp HH = h_sqr(H);
-  const Fp HHH = h_mul(H, HH);
-  const Fp V = h_mul(T.x, HH);
-  const Fp X3 = fp_sub(fp_sub(h_sqr(r), HHH), fp_add(V, V));
-  const Fp Y3 = fp_sub(h_mul(r, fp_sub(V, X3)), h_mul(T.y, HHH));
-  const Fp Z3 = h_mul(T.z, H);
-  HLine l;
-  l.c0 = fp_reduce(fp_sub(h_mul(r, xQ), h_mul(yQ, Z3)));
-  l.c1 = fp_neg(r);
-  l.c4 = Z3;
-  T.x = fp_reduce(X3);
-  T.y = fp_reduce(Y3);
-  T.z = Z3;
-  return l;
-}
-
 // ---------------------------------------------------------------- G2 walk, homogeneous coordinates
 // T = (X : Y : Z) with x = X / Z, y = Y / Z on the twist y^2 = x^3 + b', b' = 4 xi (Costello-Lange-
 // Naehrig's a = 0 formulas, scaled by 4 to clear the halves; tools/gen_wave_prog.py miller1 states
 // the same walk for the wave kernels, there with 12 xi Z carried along, which a sequential lane pair
-// does not need).  The lines are h_dbl_step's / h_add_step's times a nonzero Fp2 factor (a power of
-// the Jacobian Z), which the final exponentiation removes.  No formula inverts, so the dummy walk of
-// a masked pair from (1 : 1 : 1) is harmless.
+// does not need).  The lines are the Jacobian walk's (qfp.hpp h_dbl_step_q / h_add_step_q) times a
+// nonzero Fp2 factor (a power of the Jacobian Z), which the final exponentiation removes.  No formula
+// inverts, so the dummy walk of a masked pair from (1 : 1 : 1) is harmless.
 //
 // Bounds.  T's coordinates enter and leave every step normalised with |.| < 2p (fp_reduce's (R), or
 // an h_mul output, < 1.26p whenever both operands are < 8p: 1.25p + 64 p^2 2^-392 and p 2^-392 <
@@ -491,7 +439,7 @@ HP_D HLine h_add_step(HJac& T, const Fp& xQ, const Fp& yQ) {
 struct HProj { Fp x, y, z; };
 
 // 6 lane-pair squares + 3 lane-pair products = 6 x 392 + 3 x 588 = 4,116 MADs per lane (the Jacobian
-// h_dbl_step: 7 squares + 4 products = 5,096).
+// doubling step: 7 squares + 4 products = 5,096).
 //   E = 3 b' Z^2 = 12 xi Z^2;  line (Y^2 - E, -3 X^2, 2 Y Z)
 //   X3 = 2 X Y (Y^2 - 3E),  Y3 = (Y^2 + 3E)^2 - 12 E^2,  Z3 = 4 Y^2 (2 Y Z)
 HP_D HLine h_dbl_step_h(HProj& T) {
@@ -526,7 +474,7 @@ HP_D HLine h_dbl_step_h(HProj& T) {
 }
 
 // Mixed addition T += Q, Q affine: 2 squares + 11 products = 2 x 392 + 11 x 588 = 7,252 MADs per lane.
-// The Jacobian h_add_step is 3 squares + 10 products = 7,056, but it needs T in Jacobian form, and
+// The Jacobian addition step is 3 squares + 10 products = 7,056, but it needs T in Jacobian form, and
 // the conversion (X Z : Y Z^2 : Z) costs a square and two products more than the 196 MADs it saves;
 // there are 5 addition steps against 63 doublings.
 //   theta = Y - yQ Z, lambda = X - xQ Z;  line (theta xQ - lambda yQ, -theta, lambda)
@@ -553,6 +501,84 @@ HP_D HLine h_add_step_h(HProj& T, const Fp& xQ, const Fp& yQ) {
   T.x = X3;
   return l;
 }
+
+// ---------------------------------------------------------------- one side of the Miller loop
+// Register budget (2 waves per SIMD = 256 VGPRs per lane): a side whose P is the generator (GEN)
+// keeps no P in registers -- the line evaluation multiplies by constants -- and a walked side keeps
+// only T: Q itself is re-read from memory at the 5 addition steps instead of living in 28 VGPRs
+// through the 63 doublings.
+//
+// PT: the coordinates T walks in, the width policy's Walk
+template <class PT>
+struct SideStateT {
+  Fp xP, yP;      // P (Montgomery), both lanes (unused when GEN)
+  bool act;       // pair contributes (P != O and Q != O)
+  bool qinf;      // WALK: Q is the point at infinity (the walk runs from (1, 1), masked out)
+  uint32_t q;     // Q index
+  PT T;           // WALK: the running multiple of Q (own components)
+};
+
+template <bool GEN, class ST>
+HP_D Fp side_xP(const ST& st) { return GEN ? fp_const(hb::G1X_M) : st.xP; }
+template <bool GEN, class ST>
+HP_D Fp side_yP(const ST& st, bool negate) {
+  return GEN ? (negate ? fp_neg(fp_const(hb::G1Y_M)) : fp_const(hb::G1Y_M)) : st.yP;
+}
+
+// ---------------------------------------------------------------- the lane pair as a width policy
+// What the shared Fp12 operations above and the kernel body and final exponentiation of
+// pair_side.hpp ask of a width.  The lane pair runs every product on its own, one after the other.
+struct LanePair {
+  static constexpr int LANES = 2;
+  static HP_D bool leader() { return lp_even(); }   // writes the verdict
+  static HP_D bool value_writer() { return true; }  // each lane writes its component of the value
+  using Walk = HProj;                               // a WALK side's T is homogeneous
+  static HP_D HLine dbl_step(HProj& T) { return h_dbl_step_h(T); }
+  static HP_D HLine add_step(HProj& T, const Fp& xQ, const Fp& yQ) { return h_add_step_h(T, xQ, yQ); }
+
+  static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul(a, b); }
+  template <class A1, class B1>
+  static HP_D void mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    r0 = h6_mul(a0, b0);
+    r1 = h6_mul(h6_of(a1), h6_of(b1));
+  }
+  static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
+    r0 = h6_mul(a0, b0);
+    r1 = h6_mul_12(a1, c1, c2);  // 5 products
+  }
+  // each coefficient is reduced (one carry pass) as soon as its products exist
+  static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
+                                H6& C0, Fp& c11, Fp& c12) {
+    const Fp a0b0 = h_mul(a0, b0);
+    const Fp a1b1 = h_mul(a1, b1);
+    const Fp a4b4 = h_mul(a4, b4);
+    c11 = fp_red_l(fp_sub2l(h_mul(fp_addl(a0, a4), fp_add(b0, b4)), a0b0, a4b4));
+    c12 = fp_red_l(fp_sub2l(h_mul(fp_addl(a1, a4), fp_add(b1, b4)), a1b1, a4b4));
+    C0 = {fp_red_l(h_add_xi_l(a0b0, a4b4)), fp_red_l(fp_sub2l(h_mul(fp_addl(a0, a1), fp_add(b0, b1)), a0b0, a1b1)),
+          a1b1};
+  }
+  static HP_D H12 cyclo_sqr(const H12& f) { return h12_cyclo_sqr(f); }
+  static HP_D H12 frob1(const H12& f) { return h12_frob1(f); }
+  static HP_D H12 frob2(const H12& f) { return h12_frob2(f); }
+
+  // a side's line (c0, c1, c4) evaluated at its P: (c0, c1 xP, c4 yP), or 1 for an inactive pair
+  template <bool GEN, class ST>
+  static HP_D HLine line_at_p(const HLine& l, const ST& st, bool negate) {
+    HLine e;
+    e.c0 = st.act ? l.c0 : h_one();
+    e.c1 = st.act ? fp_mul(l.c1, side_xP<GEN>(st)) : fp_zero();
+    e.c4 = st.act ? fp_mul(l.c4, side_yP<GEN>(st, negate)) : fp_zero();
+    return e;
+  }
+  // both sides' lines of a step: raw_a() / raw_b() walk the side's T or read its table.  Side A is
+  // walked and evaluated before side B is walked.
+  template <bool G1, bool G2, class RA, class RB, class ST>
+  static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
+                              HLine& lb) {
+    la = line_at_p<G1>(raw_a(), A, false);
+    lb = line_at_p<G2>(raw_b(), B, neg2);
+  }
+};
 
 // ---------------------------------------------------------------- boundary formats
 // own component of an ABI G2 coordinate pair (x.c0 x.c1 y.c0 y.c1, 12 words each)

@@ -1,5 +1,5 @@
 // Lane-QUAD extension of the lane-pair tower (pfp.hpp), namespace hbs: FOUR lanes per pairing check
-// for the mid-size batches (k_quad.hip).
+// for the mid-size batches (k_quad.hpp).
 //
 // A quad is two lane pairs (lanes 4i, 4i+1 = pair 0; 4i+2, 4i+3 = pair 1), each laid out as in
 // pfp.hpp (even lane c0, odd lane c1).  Both pairs hold the whole check state (replicated); every
@@ -78,38 +78,13 @@ HP_D H6 h6_mul_q(const H6& a, const H6& b) {
   return {c0, c1, c2};
 }
 
-HP_D H12 h12_mul_q(const H12& a, const H12& b) {
-  H6 t0, t1;
-  h6_mul2(a.c0, b.c0, a.c1, b.c1, t0, t1);
-  const H6 s = h6_mul_q(h6_add(a.c0, a.c1), h6_add(b.c0, b.c1));
-  return h12_kcomb(t0, t1, s);
-}
-
-// complex squaring (h12_sqr): t = a0 a1 on pair 0, s = (a0 + a1)(a0 + v a1) on pair 1
-HP_D H12 h12_sqr_q(const H12& a) {
-  H6 t, s;
-  h6_mul2(a.c0, a.c1, h6_add(a.c0, a.c1), h6_red(h6_add(a.c0, h6_mul_v(a.c1))), t, s);
-  return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
-           fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
-          {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
-}
-
-// f * (la * lb) (h12_mul_lines): the six line products in three dual rounds; then t0 = f0 C0 on
-// pair 0 beside t1 = f1 (0, c11, c12) on pair 1 (h6_mul with a zero coefficient: the product with
-// it is the one wasted of the 17), and s split
-HP_D H12 h12_mul_lines_q(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1,
-                         const Fp& b4) {
-  Fp a0b0, a1b1, a4b4, t04, t14, t01;
-  h_mul2(a0, b0, a1, b1, a0b0, a1b1);
-  h_mul2(a4, b4, fp_addl(a0, a4), fp_add(b0, b4), a4b4, t04);
-  h_mul2(fp_addl(a1, a4), fp_add(b1, b4), fp_addl(a0, a1), fp_add(b0, b1), t14, t01);
-  const Fp c11 = fp_red_l(fp_sub2l(t04, a0b0, a4b4));
-  const Fp c12 = fp_red_l(fp_sub2l(t14, a1b1, a4b4));
-  const H6 C0 = {fp_red_l(h_add_xi_l(a0b0, a4b4)), fp_red_l(fp_sub2l(t01, a0b0, a1b1)), a1b1};
-  H6 t0, t1;
-  h6_mul2(f.c0, C0, f.c1, {h_zero(), c11, c12}, t0, t1);
-  const H6 s = h6_mul_q(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
-  return h12_kcomb(t0, t1, s);
+// the product (C0, (0, c11, c12)) of two sparse lines from its six Fp2 products (h12_mul_lines),
+// each coefficient reduced in one carry pass
+HP_D void h_line_comb(const Fp& a0b0, const Fp& a1b1, const Fp& a4b4, const Fp& t04, const Fp& t14, const Fp& t01,
+                      H6& C0, Fp& c11, Fp& c12) {
+  c11 = fp_red_l(fp_sub2l(t04, a0b0, a4b4));
+  c12 = fp_red_l(fp_sub2l(t14, a1b1, a4b4));
+  C0 = {fp_red_l(h_add_xi_l(a0b0, a4b4)), fp_red_l(fp_sub2l(t01, a0b0, a1b1)), a1b1};
 }
 
 // Granger-Scott squaring (h12_cyclo_sqr): nine Fp2 squares in five rounds
@@ -132,16 +107,6 @@ HP_D H12 h12_cyclo_sqr_q(const H12& f) {
   return r;
 }
 
-HP_D H12 h12_inv_q(const H12& a) {
-  H6 s0, s1;
-  h6_mul2(a.c0, a.c0, a.c1, a.c1, s0, s1);
-  const H6 t = h6_red(h6_sub(h6_red(s0), h6_red(h6_mul_v(h6_red(s1)))));
-  const H6 ti = h6_red(h6_inv(t));
-  H6 r0, r1;
-  h6_mul2(a.c0, ti, a.c1, ti, r0, r1);
-  return h12_red({r0, h6_neg(r1)});
-}
-
 HP_D H12 h12_frob1_q(const H12& f) {
   H12 r;
   r.c0.c0 = h_conj(f.c0.c0);
@@ -159,7 +124,8 @@ HP_D H12 h12_frob2_q(const H12& f) {
   return r;
 }
 
-// doubling step (h_dbl_step): eleven products in six rounds
+// doubling step, T in Jacobian coordinates; lines scaled as pairing 0.14 scales them (the Fp2 factors
+// die in the final exponentiation): eleven products in six rounds
 HP_D HLine h_dbl_step_q(HJac& T) {
   Fp A, B, C, ZZ, XB, YZ, EX, EZ, C4, F;
   h_sqr2(T.x, T.y, A, B);
@@ -185,7 +151,7 @@ HP_D HLine h_dbl_step_q(HJac& T) {
   return l;
 }
 
-// addition step (h_add_step): thirteen products in seven rounds
+// addition step (mixed, Q affine): thirteen products in seven rounds
 HP_D HLine h_add_step_q(HJac& T, const Fp& xQ, const Fp& yQ) {
   Fp YZ, U2, S2, Z3, HH, R2, HHH, V, RV, YH, RX, YZ3;
   const Fp Z1Z1 = h_sqr(T.z);
@@ -207,5 +173,57 @@ HP_D HLine h_add_step_q(HJac& T, const Fp& xQ, const Fp& yQ) {
   T.z = Z3;
   return l;
 }
+
+// ---------------------------------------------------------------- the lane quad as a width policy
+// (pfp.hpp LanePair): two products side by side.  In the shared Fp12 operations that is t and s of
+// the complex squaring, Karatsuba's t0 and t1 (for the two-line product t1 = f1 (0, c11, c12) is an
+// h6_mul with a zero coefficient: the product with it is the one wasted of the 17) and the six line
+// products in three rounds.
+struct LaneQuad {
+  static constexpr int LANES = 4;
+  static HP_D bool leader() { return (threadIdx.x & 3) == 0; }
+  static HP_D bool value_writer() { return !q_hi(); }  // pair 0
+  using Walk = HJac;
+  static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_q(T); }
+  static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_q(T, xQ, yQ); }
+
+  static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul_q(a, b); }
+  template <class A1, class B1>
+  static HP_D void mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    h6_mul2(a0, b0, h6_of(a1), h6_of(b1), r0, r1);
+  }
+  static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
+    h6_mul2(a0, b0, a1, {h_zero(), c1, c2}, r0, r1);
+  }
+  static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
+                                H6& C0, Fp& c11, Fp& c12) {
+    Fp a0b0, a1b1, a4b4, t04, t14, t01;
+    h_mul2(a0, b0, a1, b1, a0b0, a1b1);
+    h_mul2(a4, b4, fp_addl(a0, a4), fp_add(b0, b4), a4b4, t04);
+    h_mul2(fp_addl(a1, a4), fp_add(b1, b4), fp_addl(a0, a1), fp_add(b0, b1), t14, t01);
+    h_line_comb(a0b0, a1b1, a4b4, t04, t14, t01, C0, c11, c12);
+  }
+  static HP_D H12 cyclo_sqr(const H12& f) { return h12_cyclo_sqr_q(f); }
+  static HP_D H12 frob1(const H12& f) { return h12_frob1_q(f); }
+  static HP_D H12 frob2(const H12& f) { return h12_frob2_q(f); }
+
+  // LanePair::line_at_p with the two products side by side
+  template <bool GEN, class ST>
+  static HP_D HLine line_at_p(const HLine& l, const ST& st, bool negate) {
+    HLine e;
+    e.c0 = st.act ? l.c0 : h_one();
+    Fp c1, c4;
+    fp_mul2(l.c1, side_xP<GEN>(st), l.c4, side_yP<GEN>(st, negate), c1, c4);
+    e.c1 = st.act ? c1 : fp_zero();
+    e.c4 = st.act ? c4 : fp_zero();
+    return e;
+  }
+  template <bool G1, bool G2, class RA, class RB, class ST>
+  static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
+                              HLine& lb) {
+    la = line_at_p<G1>(raw_a(), A, false);
+    lb = line_at_p<G2>(raw_b(), B, neg2);
+  }
+};
 
 }  // namespace hbs

@@ -337,7 +337,7 @@ int hbh_fr_poly_eval(size_t npoly, size_t ncoef, const uint8_t* coeffs, size_t n
  *     Throughput path.
  *   HBH_IMPL_WAVE (k_wave.hip): one 64-lane wave per check; the check's Fp2 products run on 32 lane
  *     pairs side by side.  Latency path (one check: the master check of combine_and_verify_sig).
- *   HBH_IMPL_QUAD (k_quad.hip): FOUR lanes per check -- two lane pairs holding the check's state
+ *   HBH_IMPL_QUAD (k_quad.hpp): FOUR lanes per check -- two lane pairs holding the check's state
  *     side by side and splitting each step's independent products (k_pair's work per check in
  *     ~0.55 of its per-lane time).  Mid-size path: 16,384 checks are one wave per SIMD.
  *   HBH_IMPL_OCT (k_oct.hpp): EIGHT lanes per check -- four lane pairs, four independent products per

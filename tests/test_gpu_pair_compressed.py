@@ -1,6 +1,9 @@
 """HBH_IMPL_PAIR (the lane-pair kernel k_pair_verify) with the final exponentiation's powers of |x|
 taken through compressed cyclotomic squarings (csrc/k_pair.hip h_exp_abs_x): every verdict equals
 the C oracle's and HBH_IMPL_WAVE's on the same inputs, and the pairing value's bytes equal both.
+HBH_IMPL_QUAD and HBH_IMPL_OCT share the kernel body and the final-exponentiation chain
+(csrc/pair_side.hpp lane_verify, final_exp) with the plain Granger-Scott loop, and are held to the
+same verdicts and bytes.
 
 The compressed form cannot express an element whose a1 coefficient is zero; the kernel then runs the
 Granger-Scott loop for that exponentiation.  A check with a G1 or G2 operand at infinity has f = 1
@@ -23,7 +26,7 @@ from hbbft_amd.engine import g1_abi_from_uncompressed as g1a, g2_abi_from_uncomp
 
 pytestmark = pytest.mark.gpu
 
-IMPL_AUTO, IMPL_PAIR, IMPL_WAVE = 3, 4, 5
+IMPL_AUTO, IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT = 3, 4, 5, 6, 7
 SIZES = [1, 2, 33, 129]
 NDOC = 4   # shared G2 points per call: at 33 and 129 each gets a line table
 NKEY = 5
@@ -97,7 +100,7 @@ def mat():
 def both(engine, call):
     out = []
     try:
-        for impl in (IMPL_PAIR, IMPL_WAVE):
+        for impl in (IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT):
             engine.set_pairing_impl(impl)
             out.append(call())
     finally:
@@ -115,9 +118,11 @@ def expect_mixed(want, n):
 def test_sign_shape(engine, mat, n):
     items = [mat.sign_item(i) for i in range(n)]
     pks, sigs, didx, want = (list(col) for col in zip(*items))
-    pair, wave = both(engine, lambda: list(engine.verify_sig_shares(pks, sigs, mat.H, didx)))
+    pair, wave, quad, octo = both(engine, lambda: list(engine.verify_sig_shares(pks, sigs, mat.H, didx)))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
@@ -126,9 +131,11 @@ def test_walk_both_sides(engine, mat, n):
     items = [mat.sign_item(i) for i in range(n)]
     pks, sigs, didx, want = (list(col) for col in zip(*items))
     hashes = [mat.H[d] for d in didx]
-    pair, wave = both(engine, lambda: list(engine.verify_signatures(pks, sigs, hashes)))
+    pair, wave, quad, octo = both(engine, lambda: list(engine.verify_signatures(pks, sigs, hashes)))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
@@ -136,15 +143,17 @@ def test_walk_both_sides(engine, mat, n):
 def test_decrypt_shape(engine, mat, n):
     items = [mat.dec_item(i) for i in range(n)]
     shares, pks, cidx, want = (list(col) for col in zip(*items))
-    pair, wave = both(engine, lambda: list(engine.verify_dec_shares(shares, pks, mat.H, mat.W, cidx)))
+    pair, wave, quad, octo = both(engine, lambda: list(engine.verify_dec_shares(shares, pks, mat.H, mat.W, cidx)))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
 def test_pairing_value_33(engine):
-    """value_out set: PAIR writes WAVE's and the oracle's bytes (e(P, Q)^3) at 33 pairs; P = O and
-    Q = O give 1, whose exponentiations all take the Granger-Scott path."""
+    """value_out set: PAIR, QUAD and OCT write WAVE's and the oracle's bytes (e(P, Q)^3) at 33 pairs;
+    P = O and Q = O give 1, whose exponentiations all take the Granger-Scott path."""
     rng = random.Random(0x3333)
     P = [cbls.g1_mul(G1, rng.randrange(1, C.R)) for _ in range(33)]
     Q = [cbls.g2_mul(G2, rng.randrange(1, C.R)) for _ in range(33)]
@@ -152,6 +161,8 @@ def test_pairing_value_33(engine):
     P[32], Q[32] = O1, O2
     one = b"".join(c.to_bytes(48, "little") for six in C.F12_ONE for f2 in six for c in f2)
     want = [one if (p == O1 or q == O2) else cbls.pairing(p, q) for p, q in zip(P, Q)]
-    pair, wave = both(engine, lambda: engine.dbg_pairing(P, Q))
+    pair, wave, quad, octo = both(engine, lambda: engine.dbg_pairing(P, Q))
     assert pair == wave
     assert pair == want
+    assert quad == want
+    assert octo == want

@@ -1,6 +1,8 @@
 """HBH_IMPL_PAIR (the lane-pair kernel k_pair_verify), whose walked G2 side keeps T in homogeneous
 coordinates (csrc/pfp.hpp h_dbl_step_h / h_add_step_h): every verdict equals the C oracle's and
-HBH_IMPL_WAVE's on the same inputs.
+HBH_IMPL_WAVE's on the same inputs.  HBH_IMPL_QUAD and HBH_IMPL_OCT run the same kernel body
+(csrc/pair_side.hpp lane_verify) on four and eight lanes per check with the Jacobian walk, and are
+held to the same verdicts: 33 crosses an octo workgroup (32 checks) and two quad waves (16 each).
 
 Shapes: sign (verify_sig_shares: H tabled once at least 4 checks share a hash, sigma walked, P2 the
 generator), walk on both sides (verify_signatures: one hash per check) and decrypt
@@ -21,7 +23,7 @@ from hbbft_amd.engine import g1_abi_from_uncompressed as g1a, g2_abi_from_uncomp
 
 pytestmark = pytest.mark.gpu
 
-IMPL_AUTO, IMPL_PAIR, IMPL_WAVE = 3, 4, 5
+IMPL_AUTO, IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT = 3, 4, 5, 6, 7
 SIZES = [1, 2, 33, 129]
 NDOC = 4   # shared G2 points per call: 33 / 4 and 129 / 4 checks per point get a line table
 NKEY = 5
@@ -101,7 +103,7 @@ def dec_item(m, i):
 def both(engine, call):
     out = []
     try:
-        for impl in (IMPL_PAIR, IMPL_WAVE):
+        for impl in (IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT):
             engine.set_pairing_impl(impl)
             out.append(list(call()))
     finally:
@@ -120,9 +122,11 @@ def test_sign_shape(engine, mat, n):
     items = [sign_item(mat, i) for i in range(n)]
     pks, sigs, didx = [a for a, _, _ in items], [b for _, b, _ in items], [d for _, _, d in items]
     want = [int(cbls.verify_g2(pk, sig, mat.H[d])) for pk, sig, d in items]
-    pair, wave = both(engine, lambda: engine.verify_sig_shares(pks, sigs, mat.H, didx))
+    pair, wave, quad, octo = both(engine, lambda: engine.verify_sig_shares(pks, sigs, mat.H, didx))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
@@ -131,9 +135,11 @@ def test_walk_both_sides(engine, mat, n):
     items = [sign_item(mat, i) for i in range(n)]
     pks, sigs, hashes = [a for a, _, _ in items], [b for _, b, _ in items], [mat.H[d] for _, _, d in items]
     want = [int(cbls.verify_g2(pk, sig, h)) for pk, sig, h in zip(pks, sigs, hashes)]
-    pair, wave = both(engine, lambda: engine.verify_signatures(pks, sigs, hashes))
+    pair, wave, quad, octo = both(engine, lambda: engine.verify_signatures(pks, sigs, hashes))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
@@ -142,9 +148,11 @@ def test_decrypt_shape(engine, mat, n):
     items = [dec_item(mat, i) for i in range(n)]
     shares, pks, cidx = [a for a, _, _ in items], [b for _, b, _ in items], [c for _, _, c in items]
     want = [int(cbls.pairing_eq(s, mat.H[c], pk, mat.W[c])) for s, pk, c in items]
-    pair, wave = both(engine, lambda: engine.verify_dec_shares(shares, pks, mat.H, mat.W, cidx))
+    pair, wave, quad, octo = both(engine, lambda: engine.verify_dec_shares(shares, pks, mat.H, mat.W, cidx))
     assert pair == want
     assert wave == want
+    assert quad == want
+    assert octo == want
     expect_mixed(want, n)
 
 
@@ -161,8 +169,8 @@ def test_expected_verdicts_by_kind(mat):
 
 
 def test_pairing_value_33(engine, mat):
-    """value_out set (the path of test_pairing_value_matches_oracle): PAIR writes the oracle's bytes
-    (e(P, Q)^3) at 33 pairs, also for P = O, Q = O and the small multiples of g2."""
+    """value_out set (the path of test_pairing_value_matches_oracle): PAIR, QUAD and OCT write the
+    oracle's bytes (e(P, Q)^3) at 33 pairs, also for P = O, Q = O and the small multiples of g2."""
     rng = random.Random(33)
     P = [cbls.g1_mul(G1, rng.randrange(1, C.R)) for _ in range(33)]
     Q = [cbls.g2_mul(G2, rng.randrange(1, C.R)) for _ in range(33)]
@@ -171,8 +179,8 @@ def test_pairing_value_33(engine, mat):
     one = b"".join(c.to_bytes(48, "little") for six in C.F12_ONE for f2 in six for c in f2)
     want = [one if (p == O1 or q == O2) else cbls.pairing(p, q) for p, q in zip(P, Q)]
     try:
-        engine.set_pairing_impl(IMPL_PAIR)
-        got = engine.dbg_pairing(P, Q)
+        for impl in (IMPL_PAIR, IMPL_QUAD, IMPL_OCT):
+            engine.set_pairing_impl(impl)
+            assert engine.dbg_pairing(P, Q) == want, impl
     finally:
         engine.set_pairing_impl(IMPL_AUTO)
-    assert got == want

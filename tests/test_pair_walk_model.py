@@ -1,7 +1,8 @@
 """The lane-pair kernel's homogeneous G2 walk (csrc/pfp.hpp h_dbl_step_h / h_add_step_h) against
-the Jacobian walk it replaces (h_dbl_step / h_add_step), over the oracle's Fp2 arithmetic.
+the Jacobian walk it replaces (csrc/qfp.hpp h_dbl_step_q / csrc/ofp.hpp h_dbl_step_o and their
+addition steps, which the other widths keep), over the oracle's Fp2 arithmetic.
 
-Both formula sets are restated here exactly as pfp.hpp states them.  All 68 steps of |x| are
+Both formula sets are restated here exactly as pfp.hpp and qfp.hpp state them.  All 68 steps of |x| are
 walked with both; at every step the two running points must be the same affine point and the two
 lines (c0, c1, c4) must differ by one nonzero Fp2 factor (which the final exponentiation removes).
 """
@@ -19,7 +20,7 @@ def k(a, n):
     return C.f2_muls(a, n % C.P)
 
 
-# ---------------------------------------------------------------- Jacobian (h_dbl_step / h_add_step)
+# ---------------------------------------------------------------- Jacobian (h_dbl_step_q / h_add_step_q)
 def jac_dbl(T):
     X, Y, Z = T
     A = sqr(X)

@@ -345,7 +345,7 @@ class Builder:
                             name="tbl"))
                 return
             if steps[s] == "D":
-                # h_dbl_step with D = 4 X B (= 2((X+B)^2 - A - C)), levels of independent products
+                # the Jacobian doubling step (qfp.hpp h_dbl_step_q) with D = 4 X B (= 2((X+B)^2 - A - C)), levels of independent products
                 self.add(Op("M1", [[Prod(TX, TX)], [Prod(TY, TY)], [Prod(TZ, TZ)],
                                    [Prod(TY, TY, b=TZ, sb=1, d=TZ, sd=1)]],
                             [Out(T("E"), [(P_(0), 3, 0)]), Out(T("B"), [(P_(1), 1, 0)]),
@@ -366,7 +366,7 @@ class Builder:
                     outs.append(Out(l[0], [(P_(3), 1, 0)], gate=side, default="ONE"))
                 self.add(Op("M1", prods, outs, name="dbl3"))
             else:
-                # h_add_step (mixed addition with the affine Q)
+                # the Jacobian addition step (qfp.hpp h_add_step_q: mixed addition with the affine Q)
                 self.add(Op("M1", [[Prod(TZ, TZ)], [Prod(QY, TZ)]],
                             [Out(T("Z1Z1"), [(P_(0), 1, 0)]), Out(T("YQZ"), [(P_(1), 1, 0)])], name="add1"))
                 self.add(Op("M1", [[Prod(QX, T("Z1Z1"))], [Prod(T("YQZ"), T("Z1Z1"))]],
@@ -552,7 +552,7 @@ class Builder:
             self.add(op_mul_ll(LL, L(0, s), L(1, s)))
             self.add(op_mul_fl(self.F, self.F, LL))
 
-    # ---- final exponentiation (k_pair.hip h_final_exp, the chain of pairing.hpp final_exp_x3)
+    # ---- final exponentiation (pair_side.hpp final_exp, the chain of pairing.hpp final_exp_x3)
     def final_exp(self):
         F = self.F
         G, T, A, B, X1, X2, FR, R = (self.group(n) for n in ("G", "T", "A", "B", "X1", "X2", "FR", "RS"))
@@ -877,8 +877,8 @@ def const_values():
 
 
 def raw_lines(Q):
-    """Raw (c0, c1, c4) lines of the lane-pair walk (pfp.hpp h_dbl_step / h_add_step) from Q, as
-    k_pair_prep stores them; Q = None walks from (1, 1) like the kernel."""
+    """Raw (c0, c1, c4) lines of the Jacobian walk (qfp.hpp h_dbl_step_q / h_add_step_q) from Q, as
+    k_oct_prep stores them; Q = None walks from (1, 1) like the kernel."""
     xq, yq = Q if Q is not None else ((1, 0), (1, 0))
     X, Y, Z = xq, yq, (1, 0)
     out = []
