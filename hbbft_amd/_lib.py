@@ -47,6 +47,16 @@ SIGNATURES = [
     ("hbh_commit_set_size", _I, [_P, _c.POINTER(_SZ), _c.POINTER(_SZ)]),
     ("hbh_bivar_row_set", _I, [_P, _SZ, _P, _P, _P]),
     ("hbh_bivar_ack_check_set", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
+    # device-resident prepared G2 points
+    ("hbh_g2_set_create", _I, [_P, _SZ, _c.POINTER(_P)]),
+    ("hbh_g2_set_destroy", _I, [_P]),
+    ("hbh_g2_set_add", _I, [_P, _SZ, _P, _P]),
+    ("hbh_g2_set_release", _I, [_P, _SZ, _P]),
+    ("hbh_g2_set_size", _I, [_P, _c.POINTER(_SZ), _c.POINTER(_SZ)]),
+    ("hbh_verify_pairing_eq_set", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _P]),
+    ("hbh_verify_sig_shares_set", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
+    ("hbh_verify_dec_shares_set", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("hbh_verify_pairing_eq_set_dev", _I, [_P, _P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_engine_set_pairing_impl", _I, [_P, _I]),
     ("hbh_engine_set_ack_impl", _I, [_P, _I]),
     ("hbh_engine_set_decode_impl", _I, [_P, _I]),

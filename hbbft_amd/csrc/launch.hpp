@@ -27,8 +27,12 @@ struct PairSideDesc {
   size_t nq;
 };
 size_t pair_table_bytes(size_t nq);
-// the same tables from lane octos (k_oct_prep.hip: eight lanes per point)
-hipError_t oct_prep(hipStream_t s, int n, const void* q, void* lines, uint8_t* qinf);
+// the same tables from lane octos (k_oct_prep.hip: eight lanes per point).  slot == nullptr: point j
+// writes table j and qinf[j] (a call's own tables).  Slot-mapped form (resident G2 sets): point j
+// writes table slot[j] and qinf[slot[j]] of an nslot-slot set and copies its 48 ABI words to
+// qout + 48 slot[j]; a slot >= nslot writes nothing.
+hipError_t oct_prep(hipStream_t s, int n, const void* q, void* lines, uint8_t* qinf, const uint32_t* slot = nullptr,
+                    size_t nslot = 0, void* qout = nullptr);
 // flags: bit 0 negates P2 (pairing equality), bit 1 conjugates f (single pairing value, with
 // value_out: e(P1,Q1)^3 e(P2,Q2)^3 as 144 canonical words per check)
 hipError_t pair_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,

@@ -162,6 +162,81 @@ class Engine:
                                                 vp(d_i1) if d_i1 else None, vp(d_p2) if d_p2 else None, vp(d_q2), nq2,
                                                 vp(d_i2) if d_i2 else None, vp(d_v)))
 
+    # ------------------------------------------------------------ resident G2 sets
+    def g2_set(self, capacity):
+        """An empty device-resident set of ``capacity`` prepared G2 points (hbh_g2_set_create)."""
+        return G2Set(self, capacity)
+
+    @staticmethod
+    def _set_side(g2set, table, idx, n):
+        """(set handle, table keep-alive, table pointer, table size, idx keep-alive, idx pointer) of
+        one side: ``g2set`` None is a stateless side (``table`` + optional ``idx``), else ``idx``
+        holds the set's slots and ``table`` must be None."""
+        if g2set is None:
+            qb = _join(table, G2_BYTES)
+            keep = buf(qb)
+            ia, pia = _u32(idx, n)
+            return None, keep, keep[1], len(qb) // G2_BYTES, ia, pia
+        if table is not None:
+            raise ValueError("a side with a G2 set takes no table")
+        if idx is None:
+            raise ValueError("a side with a G2 set needs its slots")
+        ia, pia = _u32(idx, n)
+        return g2set._h, None, None, 0, ia, pia
+
+    def verify_pairing_eq_set(self, p1, set1, q1_table, q1_idx, p2, set2, q2_table, q2_idx):
+        """verify_pairing_eq where a side with a G2Set (set1 / set2) takes Q from the set's slots
+        (q*_table None, q*_idx the slots); a side with None is verify_pairing_eq's."""
+        p1b, p2b = _join(p1, G1_BYTES), _join(p2, G1_BYTES)
+        n = len(p1b) // G1_BYTES
+        if len(p2b) // G1_BYTES != n:
+            raise ValueError("p1/p2 length mismatch")
+        s1 = self._set_side(set1, q1_table, q1_idx, n)
+        s2 = self._set_side(set2, q2_table, q2_idx, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        keep = [buf(p1b), buf(p2b)]
+        check(self._l.hbh_verify_pairing_eq_set(self._h, n, keep[0][1], s1[0], s1[2], s1[3], s1[5],
+                                                keep[1][1], s2[0], s2[2], s2[3], s2[5],
+                                                ctypes.cast(out, ctypes.c_void_p)))
+        return bytes(out)[:n]
+
+    def verify_sig_shares_set(self, pks, sigs, docs, doc_slot):
+        """verify_sig_shares with H = slot doc_slot[i] of the G2Set ``docs``."""
+        pkb, sgb = _join(pks, G1_BYTES), _join(sigs, G2_BYTES)
+        n = len(pkb) // G1_BYTES
+        if len(sgb) // G2_BYTES != n:
+            raise ValueError("pks/sigs length mismatch")
+        di, pdi = _u32(doc_slot, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        keep = [buf(pkb), buf(sgb)]
+        check(self._l.hbh_verify_sig_shares_set(self._h, n, keep[0][1], keep[1][1], docs._h, pdi,
+                                                ctypes.cast(out, ctypes.c_void_p)))
+        return bytes(out)[:n]
+
+    def verify_dec_shares_set(self, shares, pks, cts, huv_slot, w_slot):
+        """verify_dec_shares with H_uv = slot huv_slot[i] and W = slot w_slot[i] of the G2Set ``cts``."""
+        sb, pkb = _join(shares, G1_BYTES), _join(pks, G1_BYTES)
+        n = len(sb) // G1_BYTES
+        if len(pkb) // G1_BYTES != n:
+            raise ValueError("shares/pks length mismatch")
+        hi, phi = _u32(huv_slot, n)
+        wi, pwi = _u32(w_slot, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        keep = [buf(sb), buf(pkb)]
+        check(self._l.hbh_verify_dec_shares_set(self._h, n, keep[0][1], keep[1][1], cts._h, phi, pwi,
+                                                ctypes.cast(out, ctypes.c_void_p)))
+        return bytes(out)[:n]
+
+    def verify_pairing_eq_set_dev(self, stream, n, d_p1, set1, d_q1, nq1, d_i1, d_p2, set2, d_q2, nq2, d_i2, d_v):
+        """Device-pointer variant of verify_pairing_eq_set (ints are raw device addresses): a side
+        with a G2Set passes d_q None, nq 0 and the device address of its slots."""
+        vp = ctypes.c_void_p
+        opt = lambda a: vp(a) if a else None  # noqa: E731
+        check(self._l.hbh_verify_pairing_eq_set_dev(self._h, opt(stream), n,
+                                                    opt(d_p1), set1._h if set1 is not None else None, opt(d_q1), nq1, opt(d_i1),
+                                                    opt(d_p2), set2._h if set2 is not None else None, opt(d_q2), nq2, opt(d_i2),
+                                                    vp(d_v)))
+
     # ------------------------------------------------------------ combine / scalar mult / DKG
     def _interp(self, fn, size, t, idx, pts):
         """idx: [[node index] * (t+1)] per combine; pts: matching point bytes (flat or nested)."""
@@ -473,6 +548,56 @@ class CommitSet:
     def close(self):
         if getattr(self, "_h", None):
             self._l.hbh_commit_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class G2Set:
+    """Device-resident prepared G2 points (hbh_g2_set_*): the H of a ThresholdSign document
+    (src/threshold_sign.rs:223) or the H_uv and W of a ThresholdDecrypt ciphertext
+    (src/threshold_decrypt.rs:227) is prepared once (line table + affine point in HBM) and named by
+    slot in Engine.verify_*_set, so a drain builds no table for it.  Fixed capacity; one engine."""
+
+    def __init__(self, engine, capacity):
+        self._eng, self._l = engine, engine._l
+        h = ctypes.c_void_p()
+        check(self._l.hbh_g2_set_create(engine._h, int(capacity), ctypes.byref(h)))
+        self._h = h
+
+    def add(self, points):
+        """Prepare ABI G2 points into the lowest free slots; returns their slots.  A set with too
+        few free slots raises (HBH_ERR_ARG) and adds nothing."""
+        pb = _join(points, G2_BYTES)
+        n = len(pb) // G2_BYTES
+        if n == 0:
+            return []
+        slots = (ctypes.c_uint32 * n)()
+        keep = buf(pb)
+        check(self._l.hbh_g2_set_add(self._h, n, keep[1], ctypes.cast(slots, ctypes.c_void_p)))
+        return list(slots)
+
+    def release(self, slots):
+        """Free slots for reuse (a slot that is not live raises and frees nothing)."""
+        slots = [int(s) for s in slots]
+        if not slots:
+            return
+        sa, psa = _u32(slots, len(slots))
+        check(self._l.hbh_g2_set_release(self._h, len(slots), psa))
+
+    def size(self):
+        """(live slots, capacity)."""
+        a, b = ctypes.c_size_t(), ctypes.c_size_t()
+        check(self._l.hbh_g2_set_size(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.hbh_g2_set_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -132,10 +132,22 @@ class Deferred:
 class BatchVerifier:
     """Pure, order-independent verdict cache.  ``queue_*`` records checks; ``drain`` verifies every
     queued check in one engine call per kind; ``*_valid`` returns a cached verdict (or verifies a
-    single miss immediately).  ``calls`` counts engine calls (the batching evidence in tests)."""
+    single miss immediately).  ``calls`` counts engine calls (the batching evidence in tests).
 
-    def __init__(self, engine, combine_engine=None):
+    ``g2_capacity`` > 0 keeps the G2 point of every open instance (``open_doc``: H; ``open_ct``: H_uv
+    and W) prepared in a resident set of that many slots on ``engine`` (Engine.g2_set): the points
+    opened since the last drain are added in one call when the next drain starts, the drain's share
+    checks name slots (verify_*_set), and the slots are freed when the last instance of a key is
+    released.  Keys that found no free slot take the stateless call, in the same drain.  Verdicts,
+    cache contents and counters are those of ``g2_capacity`` = 0 (the default: no set)."""
+
+    def __init__(self, engine, combine_engine=None, g2_capacity=0):
         self.eng = engine
+        self._g2 = engine.g2_set(g2_capacity) if g2_capacity > 0 else None
+        self._g2_slot = {}     # point -> slot
+        self._g2_ref = {}      # point -> open keys that use it
+        self._g2_pending = {}  # points waiting for a slot (insertion order)
+        self._g2_free = []     # slots to free once no drain is in flight
         # combines on their own engine (stream) when given: a flow that combines while a
         # drain_async is in flight then does not wait for the drain's engine call
         self.ceng = combine_engine if combine_engine is not None else engine
@@ -261,9 +273,48 @@ class BatchVerifier:
     def open_ct(self, huv, w):
         self._open_key((bytes(huv), bytes(w)))
 
+    @staticmethod
+    def _key_points(key):
+        """The G2 points of an instance key: H of a document, (H_uv, W) of a ciphertext."""
+        return (key,) if isinstance(key, bytes) else key
+
     def _open_key(self, key):
         self._open[key] = self._open.get(key, 0) + 1
         self._released.discard(key)
+        if self._g2 is not None and self._open[key] == 1:  # the key's first instance
+            for pt in self._key_points(key):
+                self._g2_ref[pt] = self._g2_ref.get(pt, 0) + 1
+                if pt not in self._g2_slot:
+                    self._g2_pending[pt] = None
+
+    def _g2_close(self, key):
+        """The last instance of ``key`` is gone: its points leave the set unless another key holds them."""
+        for pt in self._key_points(key):
+            n = self._g2_ref.get(pt, 0) - 1
+            if n > 0:
+                self._g2_ref[pt] = n
+                continue
+            self._g2_ref.pop(pt, None)
+            self._g2_pending.pop(pt, None)
+            slot = self._g2_slot.pop(pt, None)
+            if slot is not None:
+                self._g2_free.append(slot)
+
+    def _g2_sync(self):
+        """Before a drain's jobs are built (main thread): free the released slots -- only while no
+        drain is in flight, whose snapshot may still name them -- then add the pending points, as many
+        as the set has room for, in one call."""
+        if self._g2_free and not self._inflight:
+            self._g2.release(self._g2_free)
+            self._g2_free = []
+        if not self._g2_pending:
+            return
+        live, cap = self._g2.size()
+        pts = list(self._g2_pending)[:cap - live]
+        if pts:
+            for pt, slot in zip(pts, self._g2.add(pts)):
+                self._g2_slot[pt] = slot
+                del self._g2_pending[pt]
 
     def _close_key(self, key):
         """True when the last running instance of ``key`` is gone."""
@@ -273,6 +324,8 @@ class BatchVerifier:
             return False
         self._open.pop(key, None)
         self._released.add(key)
+        if self._g2 is not None:
+            self._g2_close(key)
         return True
 
     def release_doc(self, h):
@@ -405,6 +458,12 @@ class BatchVerifier:
     def _take_jobs(self):
         """Snapshot the queues as engine-call arguments (main thread)."""
         jobs = []
+        g2 = self._g2 is not None and (self._qsig or self._qdec)
+        if g2:
+            t0 = time.perf_counter()
+            self._g2_sync()
+            self.wait_s += time.perf_counter() - t0
+            slot = self._g2_slot.get
         if self._qct:
             keys = list(dict.fromkeys(self._qct))
             self._qct = []
@@ -414,20 +473,58 @@ class BatchVerifier:
             self._qsig = []
             hs = list(dict.fromkeys(k[1] for k in keys))
             hidx = {h: i for i, h in enumerate(hs)}
-            jobs.append(("sig", keys, ([k[0] for k in keys], [k[2] for k in keys], hs, [hidx[k[1]] for k in keys])))
+            args = ([k[0] for k in keys], [k[2] for k in keys], hs, [hidx[k[1]] for k in keys])
+            # with a set: the slot of each document (None: not resident) rides along as a last element
+            jobs.append(("sig", keys, args + ([slot(h) for h in hs],) if g2 else args))
         if self._qdec:
             keys = list(dict.fromkeys(self._qdec))
             self._qdec = []
             cts = list(dict.fromkeys((k[2], k[3]) for k in keys))
             cidx = {c: i for i, c in enumerate(cts)}
-            jobs.append(("dec", keys, ([k[1] for k in keys], [k[0] for k in keys], [c[0] for c in cts],
-                                       [c[1] for c in cts], [cidx[(k[2], k[3])] for k in keys])))
+            args = ([k[1] for k in keys], [k[0] for k in keys], [c[0] for c in cts], [c[1] for c in cts],
+                    [cidx[(k[2], k[3])] for k in keys])
+            # with a set: (H_uv slot, W slot) of each ciphertext, None unless both are resident
+            pairs = [(slot(c[0]), slot(c[1])) for c in cts] if g2 else None
+            jobs.append(("dec", keys, args + ([None if None in p else p for p in pairs],) if g2 else args))
         return jobs
 
     def _run_jobs(self, jobs):
         """The engine calls of a snapshot (any thread): [(kind, keys, verdict bytes)]."""
         fn = {"ct": "verify_ciphertexts", "sig": "verify_sig_shares", "dec": "verify_dec_shares"}
-        return [(kind, keys, getattr(self.eng, fn[kind])(*args)) for kind, keys, args in jobs]
+        nargs = {"ct": 3, "sig": 4, "dec": 5}
+        return [(kind, keys, getattr(self.eng, fn[kind])(*args) if len(args) == nargs[kind] else self._run_set(kind, *args))
+                for kind, keys, args in jobs]
+
+    def _run_set(self, kind, a, b, tab0, tab1, idx, slots=None):
+        """A sign or decryption job whose shared points are (partly) resident: the checks of resident
+        keys through the set call, the others through the stateless call on their own tables; the
+        verdicts come back in the job's order."""
+        if kind == "sig":  # (pks, sigs, hashes, doc_idx, slots)
+            tab0, tab1, idx, slots = (tab0,), None, tab1, idx
+        else:              # (shares, pks, huv, w, ct_idx, slots)
+            tab0 = (tab0, tab1)
+        n = len(idx)
+        res = [i for i in range(n) if slots[idx[i]] is not None]
+        ovf = [i for i in range(n) if slots[idx[i]] is None]
+        v = bytearray(n)
+        if res:
+            ra, rb = [a[i] for i in res], [b[i] for i in res]
+            if kind == "sig":
+                got = self.eng.verify_sig_shares_set(ra, rb, self._g2, [slots[idx[i]] for i in res])
+            else:
+                got = self.eng.verify_dec_shares_set(ra, rb, self._g2, [slots[idx[i]][0] for i in res],
+                                                     [slots[idx[i]][1] for i in res])
+            for i, ok in zip(res, got):
+                v[i] = ok
+        if ovf:
+            used = list(dict.fromkeys(idx[i] for i in ovf))
+            pos = {k: j for j, k in enumerate(used)}
+            oa, ob, oi = [a[i] for i in ovf], [b[i] for i in ovf], [pos[idx[i]] for i in ovf]
+            tabs = [[t[k] for k in used] for t in tab0]
+            got = (self.eng.verify_sig_shares if kind == "sig" else self.eng.verify_dec_shares)(oa, ob, *tabs, oi)
+            for i, ok in zip(ovf, got):
+                v[i] = ok
+        return bytes(v)
 
     def _store(self, results, want=None):
         """Cache verdicts (main thread).  Verdicts of instances whose last running instance

@@ -150,6 +150,54 @@ int hbh_verify_pairing_eq_dev(hbh_engine* eng, void* stream, size_t n,
                               const void* d_p2, const void* d_q2_table, size_t nq2, const uint32_t* d_q2_idx,
                               uint8_t* d_verdicts);
 
+/* Device-resident prepared G2 points (the counterpart of pairing's G2Prepared).  The shared G2 point
+ * of an instance -- H = hash_g2(doc) of a ThresholdSign document (src/threshold_sign.rs:223), H_uv and
+ * W of a ThresholdDecrypt ciphertext (src/threshold_decrypt.rs:227) -- outlives the drains that verify
+ * shares against it.  A G2 set prepares such a point once into HBM (its Miller-loop line table, its
+ * affine point and its infinity byte: 24,129 B per slot) and calls name it by slot afterwards, so a
+ * call builds no line table for that side (no HBH_STAGE_PREPARE launch) and uploads no G2 bytes for it.
+ *   hbh_g2_set_create / _destroy: `capacity` slots on `eng`, allocated once (a set never grows, its
+ *     tables never move).  Ownership as commitment sets: hbh_engine_destroy frees the device memory
+ *     and detaches the set, after which every call naming it returns HBH_ERR_ARG and
+ *     hbh_g2_set_destroy only frees the handle; a set used with another engine is HBH_ERR_ARG.
+ *   hbh_g2_set_add: prepares n points (ABI G2, the ABI's subgroup contract; a coordinate >= p is
+ *     HBH_ERR_ARG) into the lowest free slots and returns them in slots[0..n); one table launch per
+ *     call, ordered after every earlier call on any stream and before every later one.  Fewer than n
+ *     free slots: HBH_ERR_ARG, nothing is added.
+ *   hbh_g2_set_release: frees slots for reuse; a slot that is not live (or named twice) is
+ *     HBH_ERR_ARG and nothing is freed.
+ *   hbh_g2_set_size: live slots and capacity.
+ *   hbh_verify_pairing_eq_set: hbh_verify_pairing_eq where a side with a non-NULL set takes its Q from
+ *     the set: q*_table must be NULL and nq* 0, and q*_idx (required: no identity map) holds slots,
+ *     every one live, else HBH_ERR_ARG.  A side with a NULL set is exactly hbh_verify_pairing_eq's
+ *     (per-check Q or a per-call shared table); both sides may name the same set.  Same verdicts.
+ *   hbh_verify_sig_shares_set: hbh_verify_sig_shares with H = docs[doc_slot[i]].
+ *   hbh_verify_dec_shares_set: hbh_verify_dec_shares with H_uv = cts[huv_slot[i]], W = cts[w_slot[i]].
+ *   hbh_verify_pairing_eq_set_dev: hbh_verify_pairing_eq_dev likewise (same ordering between streams).
+ *     Slot arrays live in device memory and are not inspected: a slot >= capacity yields verdict 0, a
+ *     released slot is the caller's error (it reads whatever point holds the slot).
+ * With both sides resident the wave kernels (HBH_IMPL_WAVE2 / WAVE / WAVEP) read both tables at any n;
+ * with one they walk it from the stored affine point, as they walk a shared side of a small call.
+ * Sets belong to one engine: the pool has no set entry points. */
+typedef struct hbh_g2_set hbh_g2_set;
+int hbh_g2_set_create(hbh_engine* eng, size_t capacity, hbh_g2_set** out);
+int hbh_g2_set_destroy(hbh_g2_set* set);
+int hbh_g2_set_add(hbh_g2_set* set, size_t n, const uint8_t* pts, uint32_t* slots);
+int hbh_g2_set_release(hbh_g2_set* set, size_t n, const uint32_t* slots);
+int hbh_g2_set_size(const hbh_g2_set* set, size_t* live, size_t* capacity);
+int hbh_verify_pairing_eq_set(hbh_engine* eng, size_t n,
+                              const uint8_t* p1, hbh_g2_set* set1, const uint8_t* q1_table, size_t nq1, const uint32_t* q1_idx,
+                              const uint8_t* p2, hbh_g2_set* set2, const uint8_t* q2_table, size_t nq2, const uint32_t* q2_idx,
+                              uint8_t* verdicts);
+int hbh_verify_sig_shares_set(hbh_engine* eng, size_t n, const uint8_t* pks, const uint8_t* sigs,
+                              hbh_g2_set* docs, const uint32_t* doc_slot, uint8_t* verdicts);
+int hbh_verify_dec_shares_set(hbh_engine* eng, size_t n, const uint8_t* shares, const uint8_t* pks,
+                              hbh_g2_set* cts, const uint32_t* huv_slot, const uint32_t* w_slot, uint8_t* verdicts);
+int hbh_verify_pairing_eq_set_dev(hbh_engine* eng, void* stream, size_t n,
+                                  const void* d_p1, hbh_g2_set* set1, const void* d_q1_table, size_t nq1, const uint32_t* d_q1_idx,
+                                  const void* d_p2, hbh_g2_set* set2, const void* d_q2_table, size_t nq2, const uint32_t* d_q2_idx,
+                                  uint8_t* d_verdicts);
+
 /* ---------------------------------------------------------------- combine (interpolate at 0)
  * threshold_crypto interpolate(t, samples) for `ncomb` independent combines of exactly t+1
  * samples each (the first t+1 of the reference's iterator, in its order): out[c] =
