@@ -17,6 +17,11 @@
 // exponentiation one Fp12 (6 components per lane, packed to 72 words) is parked in LDS:
 // 256 lanes x 288 B = 72 KiB per workgroup, two workgroups per CU.
 #define HS_MULFN static __device__ __noinline__
+// A wave holds 32 checks with 32 different GCD traces: the six inversions of a check (h6_inv's, and
+// one per exponentiation in h_exp_tail) take the branch-free form (profiles/r13/README.md)
+#ifndef HP_INV_MODE
+#define HP_INV_MODE 12  // hb::INV_UNIFORM | hbs::INV_PAIR
+#endif
 #include "pair_side.hpp"
 
 namespace hbs {
@@ -100,7 +105,7 @@ static __device__ __noinline__ bool h_exp_tail(ExpPark& pk, bool plus1, H12& out
     park_fp(pk.pre[j], P);
   }
   if (h_is_zero(P)) return false;  // the same on both lanes of the pair (lp_both)
-  Fp I = fp_reduce(h_inv_vartime(P));
+  Fp I = fp_reduce(h_inv_vartime<HP_INV_MODE>(P));
   H12 acc;
 #pragma unroll 1
   for (int j = EXP_NPARK - 1; j >= (plus1 ? -1 : 0); j--) {

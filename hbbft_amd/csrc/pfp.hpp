@@ -27,6 +27,13 @@
 #include "sfp.hpp"
 #include "words.hpp"
 
+// words.hpp's inversion mode for the final exponentiation's inversions (h6_inv, and k_pair.hip's
+// decompression), chosen per translation unit: k_pair.hip, where every lane pair of a wave inverts a
+// different norm, takes the branch-free INV_UNIFORM; the other includers keep the per-divstep form.
+#ifndef HP_INV_MODE
+#define HP_INV_MODE 0
+#endif
+
 #define HP_D __device__ __forceinline__
 #define HP_L __attribute__((always_inline))  // on a lambda
 
@@ -137,6 +144,114 @@ HP_D Fp h_const(const uint32_t (&c0)[NL], const uint32_t (&c1)[NL]) {
 // pair-wide AND of a per-lane flag
 HP_D bool lp_both(bool v) { return (v ? 1 : 0) & dpp<DPP_SWAP>(v ? 1 : 0); }
 HP_D bool h_is_zero(const Fp& a) { return lp_both(fp_is_zero(a)); }
+// hb::words_inv_uniform (words.hpp INV_UNIFORM) with its work split over the lane pair, which inverts
+// one value: mode bit INV_PAIR beside INV_UNIFORM.  Both lanes run the 31 divsteps of a round on
+// the approximations, but each follows one column of the update matrix only (even: f0, f1; odd: g0,
+// g1) and holds one of (a, b) and one of (u, v) as its own: even a and u, odd b and v.  A lane
+// multiplies its own values by its two factors, keeps the term of its own row and sends the other to
+// its partner (one DPP swap per word), so each of the four rows is computed once per pair; the new a
+// or b travels back for the next round's approximation.  Same rounds, divsteps and value as
+// words_inv_uniform.
+constexpr int INV_PAIR = 8;
+template <int N>
+HP_D void lp_inv_uniform(const uint32_t* y, const uint32_t* mod, uint32_t* out) {
+  static_assert(N <= 15, "words_reduce_32m");
+  const bool ev = lp_even();
+  uint32_t mine[N], other[N], co[N + 1];  // even: a, b, u; odd: b, a, v
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    mine[i] = ev ? y[i] : mod[i];
+    other[i] = ev ? mod[i] : y[i];
+    co[i] = 0;
+  }
+  co[N] = 0;
+  co[0] = ev ? 1u : 0u;
+  uint32_t inv = mod[0];
+  for (int k = 0; k < 5; k++) inv *= 2u - mod[0] * inv;
+  const uint32_t minv = 0u - inv;
+  const int rounds = (2 * hb::words_bitlen<N>(mod) - 1 + 30) / 31;
+#pragma unroll 1
+  for (int r = 0; r < rounds; r++) {
+    const uint64_t am = hb::words_approx<N>(mine, hb::words_len2<N>(mine, other));
+    const uint64_t ao = (uint64_t)(uint32_t)dpp<DPP_SWAP>((int32_t)(uint32_t)am) |
+                        ((uint64_t)(uint32_t)dpp<DPP_SWAP>((int32_t)(uint32_t)(am >> 32)) << 32);
+    uint64_t ab = ev ? am : ao, bb = ev ? ao : am;
+    uint32_t c0 = ev ? 1u : 0u, c1 = ev ? 0u : 1u;  // own column: row a's and row b's factor
+#pragma unroll 1
+    for (int j = 0; j < 31; j++) {
+      uint32_t odd;
+      bool sw;
+      hb::words_divstep_ab(ab, bb, odd, sw);
+      hb::words_divstep_col(c0, c1, odd, sw);
+    }
+    // k: the factor of the own row (even a', u'; odd b', v'); s: the one of the partner's row
+    uint32_t km, ks, sm, ss;
+    hb::words_fac_split(ev ? c0 : c1, km, ks);
+    hb::words_fac_split(ev ? c1 : c0, sm, ss);
+    {
+      uint32_t t[N + 2], k[N + 2], row[N + 1];
+      hb::words_mul_sm<N, false>(mine, sm, ss, t);
+#pragma unroll
+      for (int i = 0; i < N + 2; i++) t[i] = (uint32_t)dpp<DPP_SWAP>((int32_t)t[i]);
+      hb::words_mul_sm<N, false>(mine, km, ks, k);
+      uint64_t c = 0;
+#pragma unroll
+      for (int i = 0; i < N + 2; i++) {
+        c += (uint64_t)k[i] + t[i];
+        t[i] = (uint32_t)c;
+        c >>= 32;
+      }
+#pragma unroll
+      for (int i = 0; i <= N; i++) row[i] = (t[i] >> 31) | (t[i + 1] << 1);
+      // a negated row negates its two factors: the own k, and the partner's s
+      const uint32_t fl = hb::words_abs<N + 1>(row);
+      ks ^= fl;
+      ss ^= (uint32_t)dpp<DPP_SWAP>((int32_t)fl);
+#pragma unroll
+      for (int i = 0; i < N; i++) {
+        mine[i] = row[i];
+        other[i] = (uint32_t)dpp<DPP_SWAP>((int32_t)row[i]);
+      }
+    }
+    {
+      // own coefficient <- (own k + partner's s-term + q m) / 2^31 (words_lin_sm31's sum; a word's
+      // two products, the partner's word and the carry stay below 2^64)
+      uint32_t t[N + 2], w[N + 2];
+      hb::words_mul_sm<N, true>(co, sm, ss, t);
+#pragma unroll
+      for (int i = 0; i < N + 2; i++) t[i] = (uint32_t)dpp<DPP_SWAP>((int32_t)t[i]);
+      const uint32_t xe = 0u - (co[N] >> 31);
+      const uint32_t k0 = km & ks;
+      const uint64_t q = (uint64_t)(((k0 + (co[0] ^ ks) * km + t[0]) * minv) & 0x7fffffffu);
+      uint64_t c = k0;
+#pragma unroll
+      for (int i = 0; i < N + 2; i++) {
+        const uint32_t xi = (i <= N ? co[i] : xe) ^ ks;
+        c += (uint64_t)xi * km;
+        if (i < N) c += q * mod[i];
+        c += t[i];
+        w[i] = (uint32_t)c;
+        c >>= 32;
+      }
+#pragma unroll
+      for (int i = 0; i <= N; i++) co[i] = (w[i] >> 31) | (w[i + 1] << 1);
+    }
+  }
+  // b is the odd lane's own value, v its coefficient
+  const uint32_t mine_one = hb::words_is_one<N>(mine) ? 1u : 0u;
+  const uint32_t part_one = (uint32_t)dpp<DPP_SWAP>((int32_t)mine_one);
+  const bool one = (ev ? part_one : mine_one) != 0;
+  uint32_t v[N + 1];
+#pragma unroll
+  for (int i = 0; i <= N; i++) {
+    const uint32_t pv = (uint32_t)dpp<DPP_SWAP>((int32_t)co[i]);
+    v[i] = ev ? pv : co[i];
+  }
+  hb::words_reduce_32m<N>(v, mod);
+#pragma unroll
+  for (int i = 0; i < N; i++) out[i] = one ? v[i] : 0u;
+}
+
 // 1 / a in Fp2 with a variable-time inverse of the (public) norm: both lanes invert the same norm.
 // a = 0 gives 0 (the binary Euclid loop would not terminate on a zero norm).
 template <int MODE = 0>
@@ -152,7 +267,10 @@ HP_D Fp h_inv_vartime(const Fp& a) {
 #pragma unroll
   for (int i = 0; i < 12; i++) p[i] = hb::PM2_W[i];
   p[0] += 2;  // p - 2 + 2
-  hb::words_inv_vartime<12, MODE>(w, p, r);
+  if ((MODE & INV_PAIR) != 0)
+    lp_inv_uniform<12>(w, p, r);
+  else
+    hb::words_inv_vartime<12, MODE>(w, p, r);
   return h_conj(fp_mul(a, fp_from_words(r)));
 }
 
@@ -237,7 +355,7 @@ HP_D H6 h6_inv(const H6& a) {
   // the final exponentiation's one inversion: values are public (share checks), so the binary-GCD
   // inverse (25 rounds of 31 divsteps) replaces Fermat's 380 squarings + ~190 products (A/B on one
   // box: sign 23.4 -> 22.7 ms, decrypt 21.6 -> 20.8 ms per 65,536 checks, profiles/r03/ab_inv.txt)
-  const Fp ti = fp_reduce(h_inv_vartime(t));
+  const Fp ti = fp_reduce(h_inv_vartime<HP_INV_MODE>(t));
   return {h_mul(c0, ti), h_mul(c1, ti), h_mul(c2, ti)};
 }
 

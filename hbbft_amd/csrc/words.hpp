@@ -146,9 +146,226 @@ HW_HD void words_lin_mont31(const uint32_t* x, int64_t fx, const uint32_t* y, in
 // (INV_LAZY) takes the bit length of a | b once and keeps the coefficients u, v signed and unreduced across the
 // rounds (one reduction at the end) -- fewer instructions, but more live registers: the two-wave
 // k_wave64 takes it, the 256-register k_wave does not (it spills there).
-constexpr int INV_BATCH = 1, INV_LAZY = 2;
+// Bit 2 (INV_UNIFORM) is for callers whose lanes invert DIFFERENT values (the lane-pair pairing
+// kernel: 32 checks, 32 GCD traces per wave): words_inv_uniform below, the same rounds and divsteps
+// with no data-dependent branch, so that a wave runs one instruction stream instead of every side
+// of every branch.  It ignores the other two bits.
+constexpr int INV_BATCH = 1, INV_LAZY = 2, INV_UNIFORM = 4;
+
+// A round's update factor f in (-2^31, 2^31], held in a wrapped 32-bit word (0x80000000 is +2^31:
+// -2^31 does not occur, see words_inv_uniform), as magnitude and sign mask (0 or ~0)
+HW_HD void words_fac_split(uint32_t f, uint32_t& mag, uint32_t& sgn) {
+  const uint32_t s = 0u - (f >> 31);
+  mag = (f ^ s) - s;
+  sgn = mag == 0x80000000u ? 0u : s;
+}
+// out = (x f + y g [+ q mod]) / 2^31 in N+1 words, f = +-fm and g = +-gm given as magnitude and sign
+// mask, fm + gm <= 2^31.  SIGNED: x, y are (N+1)-word two's-complement values and q in [0, 2^31) makes
+// the sum divisible by 2^31 (words_lin_mont31's contract and value); else x, y are unsigned N-word
+// values and the quotient is floored (words_lincomb_shr31's).  A negative factor multiplies the
+// complemented words and adds its magnitude once (-x = ~x + 1), so every product is unsigned and the
+// sum is right modulo 2^(32 (N+2)); a word's three products and the carry stay below 2^64.
+template <int N, bool SIGNED>
+HW_HD void words_lin_sm31(const uint32_t* x, uint32_t fm, uint32_t fs, const uint32_t* y, uint32_t gm, uint32_t gs,
+                          const uint32_t* mod, uint32_t minv, uint32_t* out) {
+  const uint32_t xe = SIGNED ? 0u - (x[N] >> 31) : 0u, ye = SIGNED ? 0u - (y[N] >> 31) : 0u;
+  const uint32_t c0 = (fm & fs) + (gm & gs);
+  uint64_t q = 0;
+  if (SIGNED) q = (uint64_t)(((c0 + (x[0] ^ fs) * fm + (y[0] ^ gs) * gm) * minv) & 0x7fffffffu);
+  uint32_t t[N + 2];
+  uint64_t c = c0;
+#pragma unroll
+  for (int i = 0; i < N + 2; i++) {
+    const uint32_t xi = (i < N + (SIGNED ? 1 : 0) ? x[i] : xe) ^ fs;
+    const uint32_t yi = (i < N + (SIGNED ? 1 : 0) ? y[i] : ye) ^ gs;
+    c += (uint64_t)xi * fm + (uint64_t)yi * gm;
+    if (SIGNED && i < N) c += q * mod[i];
+    t[i] = (uint32_t)c;
+    c >>= 32;
+  }
+#pragma unroll
+  for (int i = 0; i <= N; i++) out[i] = (t[i] >> 31) | (t[i + 1] << 1);
+}
+// t = x f modulo 2^(32 (N+2)) in N+2 words, one term of words_lin_sm31's sum: f = +-m as magnitude
+// and sign mask, x an (N+1)-word two's-complement value if SIGNED, else unsigned N words
+template <int N, bool SIGNED>
+HW_HD void words_mul_sm(const uint32_t* x, uint32_t m, uint32_t s, uint32_t* t) {
+  const uint32_t xe = SIGNED ? 0u - (x[N] >> 31) : 0u;
+  uint64_t c = m & s;
+#pragma unroll
+  for (int i = 0; i < N + 2; i++) {
+    const uint32_t xi = (i < N + (SIGNED ? 1 : 0) ? x[i] : xe) ^ s;
+    c += (uint64_t)xi * m;
+    t[i] = (uint32_t)c;
+    c >>= 32;
+  }
+}
+// |x| for an N-word two's-complement x; returns the sign mask (~0 if x was negative)
+template <int N>
+HW_HD uint32_t words_abs(uint32_t* x) {
+  const uint32_t s = 0u - (x[N - 1] >> 31);
+  uint64_t c = s & 1u;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    c += (uint64_t)(x[i] ^ s);
+    x[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  return s;
+}
+// n = max(64, len(a | b)) for N-word a, b, by selects
+template <int N>
+HW_HD int words_len2(const uint32_t* a, const uint32_t* b) {
+  int n = 64;
+#pragma unroll
+  for (int i = 2; i < N; i++) {
+    const uint32_t o = a[i] | b[i];
+    n = o ? 32 * i + 32 - __builtin_clz(o) : n;
+  }
+  return n;
+}
+// a round's 64-bit approximation of N-word x: its low 31 bits below its bits n-33 ... n-1 (n >= 64),
+// picked by selects; no shift count reaches the operand width
+template <int N>
+HW_HD uint64_t words_approx(const uint32_t* x, int n) {
+  const int s = n - 33, w = s >> 5, sh = s & 31;  // s >= 31
+  uint32_t lo = 0, mid = 0, hi = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    lo = (i == w) ? x[i] : lo;
+    mid = (i == w + 1) ? x[i] : mid;
+    hi = (i == w + 2) ? x[i] : hi;
+  }
+  const uint64_t t = (((uint64_t)lo | ((uint64_t)mid << 32)) >> sh) | ((((uint64_t)hi) << 1) << (63 - sh));
+  return ((uint64_t)x[0] & 0x7fffffffu) | (t << 31);
+}
+// one divstep on the approximations: if a is odd and a < b, (a, b) <- (b - a, a), else if a is odd,
+// a <- a - b; then a <- a / 2.  odd: mask of "a was odd"; sw: the swap was taken
+HW_HD void words_divstep_ab(uint64_t& ab, uint64_t& bb, uint32_t& odd, bool& sw) {
+  odd = 0u - ((uint32_t)ab & 1u);
+  const uint64_t bm = bb & (((uint64_t)odd << 32) | odd);
+  sw = ab < bm;
+  const uint64_t d = ab - bm, nd = bm - ab;
+  bb = sw ? ab : bb;
+  ab = (sw ? nd : d) >> 1;
+}
+// the same divstep on one column (f0, f1) or (g0, g1) of the round's update matrix
+HW_HD void words_divstep_col(uint32_t& c0, uint32_t& c1, uint32_t odd, bool sw) {
+  const uint32_t x0 = sw ? c1 : c0, x1 = sw ? c0 : c1;
+  c0 = x0 - (x1 & odd);
+  c1 = x1 << 1;
+}
+// signed (N+1)-word v, |v| < 32 m, into [0, m): v + 32 m is in (0, 64 m); subtract 2^k m, k = 5 ... 0,
+// wherever it leaves no borrow
+template <int N>
+HW_HD void words_reduce_32m(uint32_t* v, const uint32_t* mod) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i <= N; i++) {
+    const uint32_t mk = (i < N ? mod[i] << 5 : 0u) | (i > 0 ? mod[i - 1] >> 27 : 0u);
+    c += (uint64_t)v[i] + mk;
+    v[i] = (uint32_t)c;
+    c >>= 32;
+  }
+#pragma unroll
+  for (int k = 5; k >= 0; k--) {
+    uint32_t t[N + 1];
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i <= N; i++) {
+      const uint32_t mk = (i < N ? mod[i] << k : 0u) | (i > 0 ? (mod[i - 1] >> 1) >> (31 - k) : 0u);
+      const uint64_t d = (uint64_t)v[i] - mk - br;
+      t[i] = (uint32_t)d;
+      br = (d >> 63) & 1;
+    }
+#pragma unroll
+    for (int i = 0; i <= N; i++) v[i] = br ? v[i] : t[i];
+  }
+}
+
+// words_inv_vartime<N, 0>'s value by the same rounds and divsteps without a data-dependent branch
+// or loop.
+//   * A divstep selects: swap if a is odd and a < b, subtract if a is odd, halve.
+//   * The update factors are wrapped 32-bit words.  |f| + |g| <= 2^31 in each row, so 2^31 itself
+//     occurs only beside a zero: the row then says a' 2^31 = +-2^31 a (or b) on the 64-bit
+//     approximations, which are exact non-negative integers under the divsteps, and a' >= 0, a, b > 0
+//     there make the sign +.  Hence (-2^31, 2^31], and 0x80000000 reads as +2^31.
+//   * The rows are applied as magnitude and sign mask (words_lin_sm31); making a', b' non-negative
+//     flips a row's sign masks.
+//   * u, v stay signed and unreduced as in INV_LAZY: each round adds at most m to the bound, so
+//     |v| <= rounds m; v + 32 m is in (0, 64 m) and six masked subtractions of 32 m ... m bring it
+//     into [0, m).
+template <int N>
+HW_HD void words_inv_uniform(const uint32_t* y, const uint32_t* mod, uint32_t* out) {
+  static_assert(N <= 15, "rounds <= 31: |v| < 32 m, and 64 m fits N+1 words");
+  uint32_t a[N + 1], b[N + 1], u[N + 1], v[N + 1];
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    a[i] = y[i];
+    b[i] = mod[i];
+    u[i] = 0;
+    v[i] = 0;
+  }
+  a[N] = b[N] = u[N] = v[N] = 0;
+  u[0] = 1;
+  uint32_t inv = mod[0];
+  for (int k = 0; k < 5; k++) inv *= 2u - mod[0] * inv;
+  const uint32_t minv = 0u - inv;
+  const int rounds = (2 * words_bitlen<N>(mod) - 1 + 30) / 31;
+#pragma unroll 1
+  for (int r = 0; r < rounds; r++) {
+    const int n = words_len2<N>(a, b);
+    uint64_t ab = words_approx<N>(a, n), bb = words_approx<N>(b, n);
+    uint32_t f0 = 1, g0 = 0, f1 = 0, g1 = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int j = 0; j < 31; j++) {
+      uint32_t odd;
+      bool sw;
+      words_divstep_ab(ab, bb, odd, sw);
+      words_divstep_col(f0, f1, odd, sw);
+      words_divstep_col(g0, g1, odd, sw);
+    }
+    uint32_t m0, s0, m1, s1, m2, s2, m3, s3;
+    words_fac_split(f0, m0, s0);
+    words_fac_split(g0, m1, s1);
+    words_fac_split(f1, m2, s2);
+    words_fac_split(g1, m3, s3);
+    uint32_t na[N + 1], nb[N + 1];
+    words_lin_sm31<N, false>(a, m0, s0, b, m1, s1, mod, minv, na);
+    words_lin_sm31<N, false>(a, m2, s2, b, m3, s3, mod, minv, nb);
+    const uint32_t fa = words_abs<N + 1>(na), fb = words_abs<N + 1>(nb);
+    s0 ^= fa;
+    s1 ^= fa;
+    s2 ^= fb;
+    s3 ^= fb;
+#pragma unroll
+    for (int i = 0; i <= N; i++) {
+      a[i] = na[i];
+      b[i] = nb[i];
+    }
+    uint32_t nu[N + 1], nv[N + 1];
+    words_lin_sm31<N, true>(u, m0, s0, v, m1, s1, mod, minv, nu);
+    words_lin_sm31<N, true>(u, m2, s2, v, m3, s3, mod, minv, nv);
+#pragma unroll
+    for (int i = 0; i <= N; i++) {
+      u[i] = nu[i];
+      v[i] = nv[i];
+    }
+  }
+  const bool one = b[N] == 0 && words_is_one<N>(b);
+  words_reduce_32m<N>(v, mod);
+#pragma unroll
+  for (int i = 0; i < N; i++) out[i] = one ? v[i] : 0u;
+}
+
 template <int N, int MODE = 0>
 HW_HD void words_inv_vartime(const uint32_t* y, const uint32_t* mod, uint32_t* out) {
+  if ((MODE & INV_UNIFORM) != 0) {
+    words_inv_uniform<N>(y, mod, out);
+    return;
+  }
   constexpr bool BATCH = (MODE & INV_BATCH) != 0, LAZY = (MODE & INV_LAZY) != 0;
   uint32_t a[N + 1], b[N + 1], u[N + 1], v[N + 1];
 #pragma unroll
