@@ -60,6 +60,13 @@ SIGNATURES = [
     ("hbh_engine_set_pairing_impl", _I, [_P, _I]),
     ("hbh_engine_set_ack_impl", _I, [_P, _I]),
     ("hbh_engine_set_decode_impl", _I, [_P, _I]),
+    ("hbh_engine_set_hash_impl", _I, [_P, _I]),
+    ("hbh_dbg_set_hash_rounds", _I, [_P, _I]),
+    # hashing to G2 on the device
+    ("hbh_engine_hash_g2", _I, [_P, _SZ, _P, _P, _P]),
+    ("hbh_engine_hash_g1_g2", _I, [_P, _SZ, _P, _P, _P, _P]),
+    ("hbh_hash_g2_dev", _I, [_P, _P, _SZ, _P, _P]),
+    ("hbh_verify_signatures", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
     ("hbh_engine_set_profiling", _I, [_P, _I]),
     ("hbh_engine_stage_time", _I, [_P, _I, _c.POINTER(_c.c_double), _c.POINTER(_I)]),
     # device-resident variants
@@ -96,13 +103,16 @@ SIGNATURES = [
     ("hbh_hash_g1_g2_bp", _I, [_SZ, _P, _P, _P, _P, _I]),
     ("hbh_hash_bp_g1", _I, [_P]),
 ]
-STAGE_PREPARE, STAGE_PAIRING, STAGE_CURVE = 0, 1, 2
+STAGE_PREPARE, STAGE_PAIRING, STAGE_CURVE, STAGE_HASH = 0, 1, 2, 4  # HBH_STAGE_* (3 is not assigned)
 IMPL_AUTO, IMPL_PAIR, IMPL_WAVE, IMPL_QUAD, IMPL_OCT, IMPL_WAVE2 = 3, 4, 5, 6, 7, 8   # HBH_IMPL_* (0, 1, 2 = retired THREAD, LANE_COOP, THREAD_SIGNED)
 IMPL_WAVEP = 10  # HBH_IMPL_WAVEP (9 is not assigned)
 AUTO_WAVEP_MIN, AUTO_WAVEP_MAX = 1025, 1536  # HBH_AUTO_WAVEP_* (profiles/r08: the sizes where WAVEP beats WAVE by more than the spread)
 ACK_AUTO, ACK_QUAD, ACK_LANE, ACK_LANE_HORNER = 0, 1, 2, 3  # HBH_ACK_*
 DEC_AUTO, DEC_LANE, DEC_SPLIT = 0, 1, 2  # HBH_DEC_*
 AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPLIT_MAX
+HASH_AUTO, HASH_HOST, HASH_DEVICE = 0, 1, 2  # HBH_HASH_*
+HASH_ROUNDS = 32  # HBH_HASH_ROUNDS
+AUTO_HASH_DEVICE_MIN = 4096  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r14)
 
 _lib = None
 

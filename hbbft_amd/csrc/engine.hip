@@ -119,6 +119,8 @@ struct hbh_engine {
   int impl = HBH_IMPL_AUTO;  // pairing implementation (hbh_engine_set_pairing_impl)
   int ack_impl = HBH_ACK_AUTO;  // Ack-check kernel of commitment sets (hbh_engine_set_ack_impl)
   int dec_impl = HBH_DEC_AUTO;  // point-decoding kernels (hbh_engine_set_decode_impl)
+  int hash_impl = HBH_HASH_AUTO;  // where the curve half of hash_g2 runs (hbh_engine_set_hash_impl)
+  int hash_rounds = HBH_HASH_ROUNDS;  // sampler rounds of the device form (hbh_dbg_set_hash_rounds)
   StageTimer timer;
   // Completion of the last call's device work on whichever stream it ran.  Every call waits for it
   // on its own stream before touching the engine-owned workspaces, so a _dev call on a caller
@@ -161,6 +163,7 @@ struct hbh_engine {
   // Ack checks of dense y runs by finite differences (hbl::bivar_fd); HBH_ACK_FD=0: Horner only (A/B)
   bool ack_fd = true;
   DevBuf fd_e, fd_meta, fb16;
+  DevBuf hash_work, hash_state;  // the device form of hash_g2: worklists and sampled points, state bytes
   bool fb16_ready = false;  // 16-bit comb of g1 (the FD ack check), built on first use
   size_t split_max = 0;  // HBH_SPLIT_MAX: most combines per call on the split check (0: the wave rule)
   // commitment sets created on this engine: hbh_engine_destroy frees their device memory and
@@ -580,7 +583,7 @@ int hbh_engine_destroy(hbh_engine* e) {
                     &e->in_a, &e->in_b, &e->in_c, &e->in_d, &e->out_x, &e->ptab[0][0], &e->ptab[0][1], &e->ptab[1][0],
                     &e->ptab[1][1], &e->pinf[0][0], &e->pinf[0][1], &e->pinf[1][0], &e->pinf[1][1], &e->fval, &e->split_in,
                     &e->split_out, &e->tree_cnt, &e->fd_e, &e->fd_meta, &e->fb16, &e->wire_w[0], &e->wire_w[1],
-                    &e->wire_f[0], &e->wire_f[1]})
+                    &e->wire_f[0], &e->wire_f[1], &e->hash_work, &e->hash_state})
     b->release();
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   (void)hipEventDestroy(e->done);
@@ -691,6 +694,23 @@ int hbh_engine_set_decode_impl(hbh_engine* e, int impl) {
   return HBH_OK;
 }
 
+int hbh_engine_set_hash_impl(hbh_engine* e, int impl) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (impl != HBH_HASH_AUTO && impl != HBH_HASH_HOST && impl != HBH_HASH_DEVICE)
+    return fail(HBH_ERR_ARG, "unknown hash-to-G2 implementation");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->hash_impl = impl;
+  return HBH_OK;
+}
+
+int hbh_dbg_set_hash_rounds(hbh_engine* e, int rounds) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (rounds < 0 || rounds > 1024) return fail(HBH_ERR_ARG, "hash rounds out of range");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->hash_rounds = rounds ? rounds : HBH_HASH_ROUNDS;
+  return HBH_OK;
+}
+
 int hbh_engine_set_profiling(hbh_engine* e, int on) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   std::lock_guard<std::mutex> lk(e->mu);
@@ -702,7 +722,8 @@ int hbh_engine_set_profiling(hbh_engine* e, int on) {
 }
 
 int hbh_engine_stage_time(hbh_engine* e, int stage, double* total_ms, int* launches) {
-  if (!e || !total_ms || !launches || stage < 0 || stage >= HBH_NUM_STAGES) return fail(HBH_ERR_ARG, "bad argument");
+  if (!e || !total_ms || !launches || stage < 0 || stage >= HBH_NUM_STAGES || stage == 3)  // 3: not assigned
+    return fail(HBH_ERR_ARG, "bad argument");
   std::lock_guard<std::mutex> lk(e->mu);
   HBH_CHECK(hipSetDevice(e->device));
   double sum = 0;
@@ -715,6 +736,156 @@ int hbh_engine_stage_time(hbh_engine* e, int stage, double* total_ms, int* launc
   *total_ms = sum;
   *launches = (int)e->timer.ev[stage].size();
   return HBH_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- hashing to G2
+// host_hash.cpp, not part of the public ABI: seeds[i] = sha3_256 of message i (u == nullptr) or of
+// hash_g1_g2's message for (u_i, message i); the curve half of hash_g2 from one seed.
+extern "C" void hbh__hash_seeds(size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* seeds);
+extern "C" void hbh__hash_g2_seeds(size_t n, const uint32_t* which, const uint8_t* seeds, uint8_t* out);
+
+namespace {
+
+int check_msgs(size_t n, const uint8_t* data, const size_t* offsets) {
+  if (!offsets || (!data && offsets[n] != 0)) return fail(HBH_ERR_ARG, "null pointer");
+  for (size_t i = 0; i < n; i++)
+    if (offsets[i + 1] < offsets[i]) return fail(HBH_ERR_ARG, "offsets not ascending");
+  if (n > (size_t)1 << 26) return fail(HBH_ERR_ARG, "batch too large");
+  return HBH_OK;
+}
+
+bool hash_on_device(const hbh_engine* e, size_t n) {
+  if (e->hash_impl != HBH_HASH_AUTO) return e->hash_impl == HBH_HASH_DEVICE;
+  return HBH_AUTO_HASH_DEVICE_MIN != 0 && n >= HBH_AUTO_HASH_DEVICE_MIN;
+}
+
+// the kernels of the device form on s: d_seeds -> d_out, one state byte per message in e->hash_state
+int launch_hash(hbh_engine* e, hipStream_t s, size_t n, const uint8_t* d_seeds, void* d_out) {
+  HBH_CHECK(e->hash_work.ensure(hbl::hash_work_bytes(n, e->hash_rounds)));
+  HBH_CHECK(e->hash_state.ensure(n));
+  StageScope tm(e, s, HBH_STAGE_HASH);
+  HBH_CHECK(hbl::hash_g2(s, (int)n, e->hash_rounds, d_seeds, e->hash_work.p, (uint8_t*)e->hash_state.p, d_out));
+  return HBH_OK;
+}
+
+// indices of the messages the device left unresolved (more candidates than rounds)
+std::vector<uint32_t> hash_leftovers(const std::vector<uint8_t>& state) {
+  std::vector<uint32_t> left;
+  for (size_t i = 0; i < state.size(); i++)
+    if (state[i] != hbl::HASH_DONE) left.push_back((uint32_t)i);
+  return left;
+}
+
+// hbh_engine_hash_g2 / hbh_engine_hash_g1_g2 (u != nullptr)
+int run_hash_host(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* out) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!out) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_msgs(n, data, offsets);
+  if (rc) return rc;
+  bool device;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    device = hash_on_device(e, n);
+  }
+  if (!device) {
+    rc = u ? hbh_hash_g1_g2(n, u, data, offsets, out, 0) : hbh_hash_g2(n, data, offsets, out, 0);
+    return rc ? fail(rc, hbh_host_last_error()) : HBH_OK;
+  }
+  std::vector<uint8_t> seeds(n * 32), state(n);
+  hbh__hash_seeds(n, u, data, offsets, seeds.data());
+  {
+    EngineCall call(e, nullptr, true);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
+    HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
+    HBH_CHECK(e->out_x.ensure(n * HBH_G2_BYTES));
+    rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->out_x.p);
+    if (rc) return rc;
+    HBH_CHECK(download(s, out, e->out_x, n * HBH_G2_BYTES));
+    HBH_CHECK(download(s, state.data(), e->hash_state, n));
+    rc = call.finish();
+    if (rc) return rc;
+  }
+  const std::vector<uint32_t> left = hash_leftovers(state);
+  if (!left.empty()) hbh__hash_g2_seeds(left.size(), left.data(), seeds.data(), out);
+  return HBH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hbh_engine_hash_g2(hbh_engine* e, size_t n, const uint8_t* data, const size_t* offsets, uint8_t* out) {
+  return run_hash_host(e, n, nullptr, data, offsets, out);
+}
+
+int hbh_engine_hash_g1_g2(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                          uint8_t* out) {
+  if (n && !u) return fail(HBH_ERR_ARG, "null pointer");
+  return run_hash_host(e, n, u, data, offsets, out);
+}
+
+int hbh_hash_g2_dev(hbh_engine* e, void* stream, size_t n, const uint8_t* d_seeds, void* d_out) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!d_seeds || !d_out) return fail(HBH_ERR_ARG, "null pointer");
+  if (n > (size_t)1 << 26) return fail(HBH_ERR_ARG, "batch too large");
+  EngineCall call(e, stream, false);
+  if (call.rc) return call.rc;
+  const int rc = launch_hash(e, call.s, n, d_seeds, d_out);
+  if (rc) return rc;
+  return call.finish();
+}
+
+int hbh_verify_signatures(hbh_engine* e, size_t n, const uint8_t* pks, const uint8_t* sigs, const uint8_t* data,
+                          const size_t* offsets, uint8_t* v) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!pks || !sigs || !v) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_msgs(n, data, offsets);
+  if (rc) return rc;
+  bool device;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    device = hash_on_device(e, n);
+  }
+  if (!device) {
+    std::vector<uint8_t> h(n * HBH_G2_BYTES);
+    rc = hbh_hash_g2(n, data, offsets, h.data(), 0);
+    if (rc) return fail(rc, hbh_host_last_error());
+    return run_pairing_eq_host(e, n, pks, h.data(), n, nullptr, nullptr, sigs, n, nullptr, v);
+  }
+  std::vector<uint8_t> seeds(n * 32), state(n), fixed;
+  hbh__hash_seeds(n, nullptr, data, offsets, seeds.data());
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  // the hashes are written straight into the Q1 staging buffer of the pairing path and stay in HBM
+  HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
+  HBH_CHECK(e->in_q1.ensure(n * HBH_G2_BYTES));
+  rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->in_q1.p);
+  if (rc) return rc;
+  HBH_CHECK(upload(s, e->in_p1, pks, n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_q2, sigs, n * HBH_G2_BYTES));
+  HBH_CHECK(e->out_v.ensure(n));
+  HBH_CHECK(download(s, state.data(), e->hash_state, n));
+  HBH_CHECK(hipStreamSynchronize(s));
+  const std::vector<uint32_t> left = hash_leftovers(state);
+  if (!left.empty()) {  // host-hashed, then patched into the table
+    fixed.resize(n * HBH_G2_BYTES);
+    hbh__hash_g2_seeds(left.size(), left.data(), seeds.data(), fixed.data());
+    for (uint32_t i : left)
+      HBH_CHECK(h2d(s, (uint8_t*)e->in_q1.p + (size_t)i * HBH_G2_BYTES, fixed.data() + (size_t)i * HBH_G2_BYTES,
+                    HBH_G2_BYTES));
+  }
+  rc = run_pairing_sides(e, s, n, {e->in_p1.p, e->in_q1.p, nullptr, nullptr, nullptr, n},
+                         {nullptr, e->in_q2.p, nullptr, nullptr, nullptr, n}, Resident(), 1, (uint8_t*)e->out_v.p);
+  if (rc) return rc;
+  HBH_CHECK(download(s, v, e->out_v, n));
+  return call.finish();
 }
 
 }  // extern "C"

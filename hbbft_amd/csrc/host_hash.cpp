@@ -1007,3 +1007,27 @@ extern "C" int hbh__host_g1_neg(const uint8_t* pk, uint8_t* neg_out) {
   hh::g1_to_abi(hh::jac_neg(p), neg_out);
   return HBH_OK;
 }
+
+// Not part of the public ABI (engine.hip's device form of hash_g2 / hash_g1_g2): the host half of the
+// hash -- seeds[i] = sha3_256 of message i, or of hash_g1_g2's message for (u_i, message i) when u is
+// given -- and the curve half from a seed, for the messages the device leaves to the host stage:
+// out[which[k]] = G2::rand(ChaChaRng::from_seed(seeds[which[k]])).
+extern "C" void hbh__hash_seeds(size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* seeds) {
+  hh::parallel_for(n, 0, [&](size_t i) {
+    const uint8_t* m = data + offsets[i];
+    const size_t len = offsets[i + 1] - offsets[i];
+    if (u) {
+      const std::vector<uint8_t> gm = hh::g1_g2_msg(u + i * HBH_G1_BYTES, m, len);
+      hh::sha3_256(gm.data(), gm.size(), seeds + i * 32);
+    } else {
+      hh::sha3_256(m, len, seeds + i * 32);
+    }
+  });
+}
+extern "C" void hbh__hash_g2_seeds(size_t n, const uint32_t* which, const uint8_t* seeds, uint8_t* out) {
+  hh::parallel_for(n, 0, [&](size_t k) {
+    const size_t i = which[k];
+    hh::ChaChaRng rng(seeds + i * 32);
+    hh::g2_to_abi(hh::g2_mul_gls(hh::g2_rand_bp(rng), hh::KCOF), out + i * HBH_G2_BYTES);
+  });
+}

@@ -155,4 +155,14 @@ hipError_t index_plus_one(hipStream_t s, int n, int m, const uint32_t* idx, uint
 hipError_t commit_eval(hipStream_t s, int n, int t, const void* commits, const uint32_t* commit_idx, const uint32_t* xs,
                        void* out);
 
+// --------------------------------------------------------------- hashing to G2 (k_hash.hip)
+// The curve half of threshold_crypto hash_g2 for n 32-byte seeds (sha3_256 of each message) in device
+// memory: out = n ABI G2 points, state = one byte per message.  `rounds` sampler rounds, each trying the
+// next candidate x of every message that has no point yet, then the cofactor multiplication.  A message
+// that needed more candidates than rounds ends with state != HASH_DONE and an all-zero point.
+// Asynchronous on s; work = hash_work_bytes(n, rounds) bytes.
+constexpr uint8_t HASH_PENDING = 0, HASH_SAMPLED = 1, HASH_DONE = 2, HASH_FAILED = 3;
+size_t hash_work_bytes(size_t n, int rounds);
+hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out);
+
 }  // namespace hbl

@@ -53,12 +53,14 @@ __device__ __forceinline__ bool f2_gt_canon(const Fp2& a, const Fp2& b) {
 //                                  y = a1 w / 2 - (t w) u
 // (t (a0 - s)/2 = -a1^2 / 4 is a non-square for a1 != 0, so exactly one case holds.)  Any root:
 // the caller picks the sign.  false when a is not a square.
-__device__ __forceinline__ bool f2_sqrt_norm(const Fp2& a, Fp2& out) {
-  out = f2_zero();
-  if (f2_is_zero(a)) return true;
+// The two chains apart (k_hash.hip rejects a sampled x after the first): f2_sqrt_norm_first decides
+// whether a != 0 is a square and leaves s = sqrt(N); f2_sqrt_norm_second takes the root from s.
+__device__ __forceinline__ bool f2_sqrt_norm_first(const Fp2& a, Fp& s) {
   const Fp nrm = fp_add(fp_sqr(a.c0), fp_sqr(a.c1));
-  const Fp s = fp_mul(nrm, fp_pow_pm3d4(nrm));
-  if (!fp_eq(fp_sqr(s), nrm)) return false;
+  s = fp_mul(nrm, fp_pow_pm3d4(nrm));
+  return fp_eq(fp_sqr(s), nrm);
+}
+__device__ __forceinline__ bool f2_sqrt_norm_second(const Fp2& a, const Fp& s, Fp2& out) {
   const Fp half = fp_const(INV2_M);
   Fp t = fp_mul(fp_add(a.c0, s), half);
   if (fp_is_zero(t)) t = fp_mul(fp_sub(a.c0, s), half);
@@ -69,6 +71,13 @@ __device__ __forceinline__ bool f2_sqrt_norm(const Fp2& a, Fp2& out) {
   const Fp2 y = qr ? Fp2{tw, aw} : Fp2{aw, fp_neg(tw)};
   out = y;
   return f2_is_zero(f2_sub(f2_sqr(y), a));
+}
+__device__ __forceinline__ bool f2_sqrt_norm(const Fp2& a, Fp2& out) {
+  out = f2_zero();
+  if (f2_is_zero(a)) return true;
+  Fp s;
+  if (!f2_sqrt_norm_first(a, s)) return false;
+  return f2_sqrt_norm_second(a, s, out);
 }
 
 // G2: ym = the root of rhs named by the flags; false when rhs is not a square

@@ -61,10 +61,11 @@ class DhbKeyGen:
     (KeyGenState::public_keys, the validator set being generated; None when no key generation)."""
 
     def __init__(self, engine, era, our_id, secret_key, public_keys, key_gen=None, candidate_keys=None,
-                 is_validator=True, threads=0):
+                 is_validator=True, threads=0, device_hash=False):
         self.engine, self.era, self.our_id = engine, era, our_id
         self.secret_key = secret_key
         self.public_keys = dict(public_keys)
+        self.device_hash = device_hash  # batch checks hash their messages in the engine (verify_signed)
         self.key_gen = key_gen
         self.candidate_keys = dict(candidate_keys or {})
         self.is_validator = is_validator
@@ -95,9 +96,10 @@ class DhbKeyGen:
     def verify_signatures(self, items):
         """verify_signature (:514-526) for [(node_id, sig, kg_msg)]: valid under the current key OR
         the candidate key -- every check of the list in one engine call."""
-        hs = hoststage.hash_g2([key_gen_msg_bytes(m) for _, _, m in items], threads=self.threads) if items else []
+        msgs = [key_gen_msg_bytes(m) for _, _, m in items]
+        hs = hoststage.hash_g2(msgs, threads=self.threads) if items and not self.device_hash else []
         pks, sigs, hidx, owner = [], [], [], []
-        for k, ((nid, sig, _), h) in enumerate(zip(items, hs)):
+        for k, (nid, sig, _) in enumerate(items):
             seen = set()
             for keys in (self.public_keys, self.candidate_keys if self.key_gen is not None else {}):
                 pk = keys.get(nid)
@@ -109,7 +111,10 @@ class DhbKeyGen:
                     owner.append(k)
         ok = [False] * len(items)
         if pks:
-            v = self.engine.verify_sig_shares(pks, sigs, hs, hidx)
+            if self.device_hash:  # one hash per check: a message checked under two keys is hashed twice
+                v = self.engine.verify_signed(pks, sigs, [msgs[k] for k in hidx])
+            else:
+                v = self.engine.verify_sig_shares(pks, sigs, hs, hidx)
             self.calls += 1
             self.checks += len(pks)
             for k, good in zip(owner, v):
@@ -266,10 +271,11 @@ class VoteCounter:
     {node_id: ABI G1} (NetworkInfo::public_key); num_faulty: f.  ``calls`` / ``checks`` count the
     engine calls and the signatures they verified."""
 
-    def __init__(self, engine, era, our_id, secret_key, public_keys, num_faulty, threads=0):
+    def __init__(self, engine, era, our_id, secret_key, public_keys, num_faulty, threads=0, device_hash=False):
         self.engine, self.era, self.our_id = engine, era, our_id
         self.secret_key = secret_key
         self.public_keys = dict(public_keys)
+        self.device_hash = device_hash  # validate() hashes the votes in the engine (verify_signed)
         self.num_faulty = num_faulty
         self.threads = threads
         self.pending = {}    # voter -> SignedVote
@@ -291,9 +297,12 @@ class VoteCounter:
         ok = [False] * len(signed_votes)
         idx = [k for k, sv in enumerate(signed_votes) if sv.voter in self.public_keys]
         if idx:
-            hs = hoststage.hash_g2(vote_bytes([signed_votes[k].vote for k in idx]), threads=self.threads)
-            v = self.engine.verify_signatures([self.public_keys[signed_votes[k].voter] for k in idx],
-                                              [signed_votes[k].sig for k in idx], hs)
+            msgs = vote_bytes([signed_votes[k].vote for k in idx])
+            pks, sigs = [self.public_keys[signed_votes[k].voter] for k in idx], [signed_votes[k].sig for k in idx]
+            if self.device_hash:
+                v = self.engine.verify_signed(pks, sigs, msgs)
+            else:
+                v = self.engine.verify_signatures(pks, sigs, hoststage.hash_g2(msgs, threads=self.threads))
             self.calls += 1
             self.checks += len(idx)
             for k, good in zip(idx, v):

@@ -122,6 +122,66 @@ class Engine:
         n = len(_join(pks, G1_BYTES)) // G1_BYTES
         return self.verify_sig_shares(pks, sigs, hashes, list(range(n)))
 
+    def verify_signed(self, pks, sigs, msgs):
+        """PublicKey::verify(sig, msg) batch from the messages themselves (hbh_verify_signatures):
+        verify_signatures with hash_g2(msg) computed inside the call -- on the device for large batches
+        (set_hash_impl), where the hashes never leave HBM."""
+        from .hoststage import _concat
+        pkb, sgb = _join(pks, G1_BYTES), _join(sigs, G2_BYTES)
+        n = len(pkb) // G1_BYTES
+        if len(sgb) // G2_BYTES != n or len(msgs) != n:
+            raise ValueError("pks/sigs/msgs length mismatch")
+        data, offs = _concat(msgs)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        keep = [buf(pkb), buf(sgb), buf(data or b"\0")]
+        check(self._l.hbh_verify_signatures(self._h, n, keep[0][1], keep[1][1], keep[2][1],
+                                            offs.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+        return bytes(out)[:n]
+
+    # ------------------------------------------------------------ hashing to G2
+    def hash_g2(self, msgs):
+        """threshold_crypto hash_g2 per message -> ABI G2 points, the bytes of hoststage.hash_g2
+        (hbh_engine_hash_g2: SHA3 on the host, the curve half on the device for large batches)."""
+        from .hoststage import _concat
+        n = len(msgs)
+        data, offs = _concat(msgs)
+        out = (ctypes.c_uint8 * max(n * G2_BYTES, 1))()
+        keep = buf(data or b"\0")
+        check(self._l.hbh_engine_hash_g2(self._h, n, keep[1], offs.ctypes.data_as(ctypes.c_void_p),
+                                         ctypes.cast(out, ctypes.c_void_p)))
+        raw = bytes(out)
+        return [raw[i * G2_BYTES:(i + 1) * G2_BYTES] for i in range(n)]
+
+    def hash_g1_g2(self, us, vs):
+        """hash_g1_g2(U, V) per ciphertext, the bytes of hoststage.hash_g1_g2 (hbh_engine_hash_g1_g2)."""
+        from .hoststage import _concat
+        n = len(us)
+        if len(vs) != n:
+            raise ValueError("us / vs length mismatch")
+        data, offs = _concat(vs)
+        out = (ctypes.c_uint8 * max(n * G2_BYTES, 1))()
+        keep = [buf(_join(us, G1_BYTES) or b"\0"), buf(data or b"\0")]
+        check(self._l.hbh_engine_hash_g1_g2(self._h, n, keep[0][1], keep[1][1], offs.ctypes.data_as(ctypes.c_void_p),
+                                            ctypes.cast(out, ctypes.c_void_p)))
+        raw = bytes(out)
+        return [raw[i * G2_BYTES:(i + 1) * G2_BYTES] for i in range(n)]
+
+    def hash_g2_dev(self, stream, n, d_seeds, d_out):
+        """Device-pointer form (hbh_hash_g2_dev): n 32-byte seeds (sha3_256 of each message) in HBM ->
+        n ABI G2 points in HBM, asynchronous.  A message that needed more candidates than the sampler's
+        rounds is left as the all-zero point (hash_g2 never returns it): hash it on the host stage."""
+        vp = ctypes.c_void_p
+        check(self._l.hbh_hash_g2_dev(self._h, vp(stream) if stream else None, n, vp(d_seeds), vp(d_out)))
+
+    def set_hash_impl(self, impl):
+        """HBH_HASH_*: 0 = auto (default: the device from AUTO_HASH_DEVICE_MIN messages per call), 1 = the
+        host stage, 2 = the device.  Governs hash_g2, hash_g1_g2 and verify_signed; same bytes either way."""
+        check(self._l.hbh_engine_set_hash_impl(self._h, int(impl)))
+
+    def dbg_set_hash_rounds(self, rounds):
+        """Sampler rounds of the device hash (hbh_dbg_set_hash_rounds; 0 restores the default): tests only."""
+        check(self._l.hbh_dbg_set_hash_rounds(self._h, int(rounds)))
+
     def verify_dec_shares(self, shares, pks, huv, w, ct_idx):
         """PublicKeyShare::verify_decryption_share batch (src/threshold_decrypt.rs:220-229)."""
         sb, pkb = _join(shares, G1_BYTES), _join(pks, G1_BYTES)

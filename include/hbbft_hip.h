@@ -320,6 +320,44 @@ int hbh_g2_decompress(hbh_engine* eng, size_t n, const uint8_t* in, uint8_t* out
 #define HBH_AUTO_DEC_G2_SPLIT_MAX 8192
 int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
 
+/* ---------------------------------------------------------------- hashing to G2 on the device
+ * threshold_crypto hash_g2 / hash_g1_g2 for large batches of PUBLIC inputs (documents, signed messages,
+ * the (U, V) of ciphertexts; hbh_encrypt and every secret-key operation keep the host stage).  SHA3 and
+ * the message assembly run on the host (hbh_hash_g2's code and worker threads); the curve half --
+ * sampling x from the seeded ChaCha20 stream, the square root, the sign choice and the cofactor
+ * multiplication (csrc/hash_sample.hpp, k_hash.hip) -- runs on the GPU.  Output bytes are hbh_hash_g2's.
+ * This is a throughput form: one lane walks a whole hash, which takes milliseconds, so small calls
+ * belong on the host stage (hbh_engine_set_hash_impl).
+ *   hbh_engine_hash_g2 / hbh_engine_hash_g1_g2: arguments and output as hbh_hash_g2 / hbh_hash_g1_g2.
+ *   hbh_hash_g2_dev: d_seeds = n 32-byte seeds (sha3_256 of each message) in HBM, d_out = n ABI G2 points
+ *     in HBM; asynchronous on `stream` and ordered like the other _dev calls.  The sampler runs a fixed
+ *     number of rounds (HBH_HASH_ROUNDS: one candidate x per unresolved message and round, each a square
+ *     with probability 1/2).  A message that needed more candidates is UNRESOLVED: its output is the
+ *     all-zero point, which hash_g2 never returns (h2 (x, y) = O is resampled); the caller hashes it with
+ *     hbh_hash_g2.  The host-pointer calls do that themselves, so their outputs are always complete.
+ *   hbh_verify_signatures: PublicKey::verify(sig, msg) in one call (DHB signed votes and key-gen messages,
+ *     src/dynamic_honey_badger/votes.rs:157, dynamic_honey_badger.rs:520):
+ *     verdict[i] = e(pk[i], hash_g2(msg_i)) == e(g1, sig[i]), messages as hbh_hash_g2's.  On the device form
+ *     the hashes never leave HBM: they are the Q1 table of hbh_verify_pairing_eq under the identity map.
+ *   hbh_engine_set_hash_impl: HBH_HASH_HOST (the host stage, hbh_hash_g2's workers), HBH_HASH_DEVICE, or
+ *     HBH_HASH_AUTO (the default): DEVICE for calls of at least HBH_AUTO_HASH_DEVICE_MIN messages (0:
+ *     never), HOST below.  Governs the three host-pointer calls; same bytes and verdicts from either.
+ *     Threshold: the smallest swept size from which DEVICE's median host-to-host time is below HOST's by
+ *     more than both cells' min-max spread, at that and every larger swept size (profiles/r14/README.md,
+ *     tools/hash_bench.py).  Any other value returns HBH_ERR_ARG and changes nothing. */
+#define HBH_HASH_AUTO 0
+#define HBH_HASH_HOST 1
+#define HBH_HASH_DEVICE 2
+#define HBH_HASH_ROUNDS 32
+#define HBH_AUTO_HASH_DEVICE_MIN 4096
+int hbh_engine_hash_g2(hbh_engine* eng, size_t n, const uint8_t* data, const size_t* offsets, uint8_t* out);
+int hbh_engine_hash_g1_g2(hbh_engine* eng, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                          uint8_t* out);
+int hbh_hash_g2_dev(hbh_engine* eng, void* stream, size_t n, const uint8_t* d_seeds, void* d_out);
+int hbh_verify_signatures(hbh_engine* eng, size_t n, const uint8_t* pks, const uint8_t* sigs, const uint8_t* data,
+                          const size_t* offsets, uint8_t* verdicts);
+int hbh_engine_set_hash_impl(hbh_engine* eng, int impl);
+
 /* ---------------------------------------------------------------- host stage (CPU, no engine)
  * What the north star keeps on the host, batched over `threads` std::thread workers (0 = all
  * hardware threads).  Variable-length inputs are concatenated in `data` with n+1 ascending byte
@@ -465,7 +503,8 @@ int hbh_engine_set_ack_impl(hbh_engine* eng, int impl);
 #define HBH_STAGE_PREPARE 0 /* Miller-loop line tables (G2 walks) */
 #define HBH_STAGE_PAIRING 1 /* multi-Miller loop + final exponentiation */
 #define HBH_STAGE_CURVE 2   /* scalar multiplication / interpolation / bivariate checks */
-#define HBH_NUM_STAGES 3
+#define HBH_STAGE_HASH 4    /* hashing to G2: sampler rounds + cofactor multiplication (one entry per call) */
+#define HBH_NUM_STAGES 5    /* 3 is not assigned: hbh_engine_stage_time keeps answering HBH_ERR_ARG for it */
 int hbh_engine_set_profiling(hbh_engine* eng, int on);
 int hbh_engine_stage_time(hbh_engine* eng, int stage, double* total_ms, int* launches);
 
@@ -474,6 +513,10 @@ int hbh_engine_stage_time(hbh_engine* eng, int stage, double* total_ms, int* lau
  * c0.c1.c0, ... c1.c2.c1; 48 B LE each = 576 B) -- the pairing value itself, for parity tests
  * against the oracle (the kernel's final exponentiation uses the exponent 3(p^12-1)/r). */
 int hbh_dbg_pairing(hbh_engine* eng, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out);
+/* hbh_dbg_set_hash_rounds: sampler rounds of the device form of hash_g2 (1..1024; 0 restores
+ * HBH_HASH_ROUNDS).  A low value leaves messages unresolved on purpose, for the tests of the host-stage
+ * path of the leftovers and of hbh_hash_g2_dev's report. */
+int hbh_dbg_set_hash_rounds(hbh_engine* eng, int rounds);
 
 #ifdef __cplusplus
 }
