@@ -67,6 +67,9 @@ SIGNATURES = [
     ("hbh_engine_hash_g1_g2", _I, [_P, _SZ, _P, _P, _P, _P]),
     ("hbh_hash_g2_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("hbh_verify_signatures", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
+    ("hbh_engine_hash_g1_g2_bp", _I, [_P, _SZ, _P, _P, _P, _P]),
+    ("hbh_verify_ciphertexts_uv", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
+    ("hbh_engine_encrypt", _I, [_P, _SZ, _P, _I, _P, _P, _P, _P, _P, _P]),
     ("hbh_engine_set_profiling", _I, [_P, _I]),
     ("hbh_engine_stage_time", _I, [_P, _I, _c.POINTER(_c.c_double), _c.POINTER(_I)]),
     # device-resident variants
@@ -99,6 +102,8 @@ SIGNATURES = [
     ("hbh_host_g2_mul", _I, [_SZ, _P, _P, _P, _I]),
     ("hbh_host_g1_add", _I, [_SZ, _P, _P, _P]),
     ("hbh_encrypt", _I, [_SZ, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
+    ("hbh_encrypt_uv", _I, [_SZ, _P, _I, _P, _P, _P, _P, _P, _I]),
+    ("hbh_encrypt_w", _I, [_SZ, _P, _P, _P, _I]),
     ("hbh_fr_poly_eval", _I, [_SZ, _SZ, _P, _SZ, _P, _P, _I]),
     ("hbh_hash_g1_g2_bp", _I, [_SZ, _P, _P, _P, _P, _I]),
     ("hbh_hash_bp_g1", _I, [_P]),

@@ -164,6 +164,7 @@ struct hbh_engine {
   bool ack_fd = true;
   DevBuf fd_e, fd_meta, fb16;
   DevBuf hash_work, hash_state;  // the device form of hash_g2: worklists and sampled points, state bytes
+  std::vector<uint8_t> g1k;  // G1K = [KCOF^-1] g1 (hbh_hash_bp_g1), made by the first hbh_verify_ciphertexts_uv
   bool fb16_ready = false;  // 16-bit comb of g1 (the FD ack check), built on first use
   size_t split_max = 0;  // HBH_SPLIT_MAX: most combines per call on the split check (0: the wave rule)
   // commitment sets created on this engine: hbh_engine_destroy frees their device memory and
@@ -745,6 +746,8 @@ int hbh_engine_stage_time(hbh_engine* e, int stage, double* total_ms, int* launc
 // hash_g1_g2's message for (u_i, message i); the curve half of hash_g2 from one seed.
 extern "C" void hbh__hash_seeds(size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* seeds);
 extern "C" void hbh__hash_g2_seeds(size_t n, const uint32_t* which, const uint8_t* seeds, uint8_t* out);
+// the same for the Q form: out[which[k]] = Q_bp of that seed (hbh_hash_g1_g2_bp's bytes)
+extern "C" void hbh__hash_g2_bp_seeds(size_t n, const uint32_t* which, const uint8_t* seeds, uint8_t* out);
 
 namespace {
 
@@ -762,11 +765,12 @@ bool hash_on_device(const hbh_engine* e, size_t n) {
 }
 
 // the kernels of the device form on s: d_seeds -> d_out, one state byte per message in e->hash_state
-int launch_hash(hbh_engine* e, hipStream_t s, size_t n, const uint8_t* d_seeds, void* d_out) {
+int launch_hash(hbh_engine* e, hipStream_t s, size_t n, const uint8_t* d_seeds, void* d_out,
+                hbl::HashForm form = hbl::HASH_FORM_FULL) {
   HBH_CHECK(e->hash_work.ensure(hbl::hash_work_bytes(n, e->hash_rounds)));
   HBH_CHECK(e->hash_state.ensure(n));
   StageScope tm(e, s, HBH_STAGE_HASH);
-  HBH_CHECK(hbl::hash_g2(s, (int)n, e->hash_rounds, d_seeds, e->hash_work.p, (uint8_t*)e->hash_state.p, d_out));
+  HBH_CHECK(hbl::hash_g2(s, (int)n, e->hash_rounds, d_seeds, e->hash_work.p, (uint8_t*)e->hash_state.p, d_out, form));
   return HBH_OK;
 }
 
@@ -778,8 +782,32 @@ std::vector<uint32_t> hash_leftovers(const std::vector<uint8_t>& state) {
   return left;
 }
 
-// hbh_engine_hash_g2 / hbh_engine_hash_g1_g2 (u != nullptr)
-int run_hash_host(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* out) {
+// the device form for host buffers: seeds up, the points (FULL: hash_g2's, BP: Q_bp) down, the leftovers of
+// the sampler rounds hashed on the host stage
+int hash_seeds_device(hbh_engine* e, size_t n, const std::vector<uint8_t>& seeds, hbl::HashForm form, uint8_t* out) {
+  std::vector<uint8_t> state(n);
+  {
+    EngineCall call(e, nullptr, true);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
+    HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
+    HBH_CHECK(e->out_x.ensure(n * HBH_G2_BYTES));
+    int rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->out_x.p, form);
+    if (rc) return rc;
+    HBH_CHECK(download(s, out, e->out_x, n * HBH_G2_BYTES));
+    HBH_CHECK(download(s, state.data(), e->hash_state, n));
+    rc = call.finish();
+    if (rc) return rc;
+  }
+  const std::vector<uint32_t> left = hash_leftovers(state);
+  if (!left.empty())
+    (form == hbl::HASH_FORM_BP ? hbh__hash_g2_bp_seeds : hbh__hash_g2_seeds)(left.size(), left.data(), seeds.data(), out);
+  return HBH_OK;
+}
+
+// hbh_engine_hash_g2 / hbh_engine_hash_g1_g2 (u != nullptr) / hbh_engine_hash_g1_g2_bp (u != nullptr, BP)
+int run_hash_host(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets, uint8_t* out,
+                  hbl::HashForm form = hbl::HASH_FORM_FULL) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (n == 0) return HBH_OK;
   if (!out) return fail(HBH_ERR_ARG, "null pointer");
@@ -791,27 +819,15 @@ int run_hash_host(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data
     device = hash_on_device(e, n);
   }
   if (!device) {
-    rc = u ? hbh_hash_g1_g2(n, u, data, offsets, out, 0) : hbh_hash_g2(n, data, offsets, out, 0);
+    if (form == hbl::HASH_FORM_BP)
+      rc = hbh_hash_g1_g2_bp(n, u, data, offsets, out, 0);
+    else
+      rc = u ? hbh_hash_g1_g2(n, u, data, offsets, out, 0) : hbh_hash_g2(n, data, offsets, out, 0);
     return rc ? fail(rc, hbh_host_last_error()) : HBH_OK;
   }
-  std::vector<uint8_t> seeds(n * 32), state(n);
+  std::vector<uint8_t> seeds(n * 32);
   hbh__hash_seeds(n, u, data, offsets, seeds.data());
-  {
-    EngineCall call(e, nullptr, true);
-    if (call.rc) return call.rc;
-    hipStream_t s = call.s;
-    HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
-    HBH_CHECK(e->out_x.ensure(n * HBH_G2_BYTES));
-    rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->out_x.p);
-    if (rc) return rc;
-    HBH_CHECK(download(s, out, e->out_x, n * HBH_G2_BYTES));
-    HBH_CHECK(download(s, state.data(), e->hash_state, n));
-    rc = call.finish();
-    if (rc) return rc;
-  }
-  const std::vector<uint32_t> left = hash_leftovers(state);
-  if (!left.empty()) hbh__hash_g2_seeds(left.size(), left.data(), seeds.data(), out);
-  return HBH_OK;
+  return hash_seeds_device(e, n, seeds, form, out);
 }
 
 }  // namespace
@@ -826,6 +842,12 @@ int hbh_engine_hash_g1_g2(hbh_engine* e, size_t n, const uint8_t* u, const uint8
                           uint8_t* out) {
   if (n && !u) return fail(HBH_ERR_ARG, "null pointer");
   return run_hash_host(e, n, u, data, offsets, out);
+}
+
+int hbh_engine_hash_g1_g2_bp(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                             uint8_t* out) {
+  if (n && !u) return fail(HBH_ERR_ARG, "null pointer");
+  return run_hash_host(e, n, u, data, offsets, out, hbl::HASH_FORM_BP);
 }
 
 int hbh_hash_g2_dev(hbh_engine* e, void* stream, size_t n, const uint8_t* d_seeds, void* d_out) {
@@ -886,6 +908,95 @@ int hbh_verify_signatures(hbh_engine* e, size_t n, const uint8_t* pks, const uin
   if (rc) return rc;
   HBH_CHECK(download(s, v, e->out_v, n));
   return call.finish();
+}
+
+int hbh_verify_ciphertexts_uv(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                              const uint8_t* w, uint8_t* v) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!u || !w || !v) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_msgs(n, data, offsets);
+  if (rc) return rc;
+  bool device;
+  std::vector<uint8_t> g1k(n * HBH_G1_BYTES);  // P1 = G1K for every check
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    device = hash_on_device(e, n);
+    if (e->g1k.empty()) {
+      e->g1k.resize(HBH_G1_BYTES);
+      rc = hbh_hash_bp_g1(e->g1k.data());
+      if (rc) {
+        e->g1k.clear();
+        return fail(rc, hbh_host_last_error());
+      }
+    }
+    for (size_t i = 0; i < n; i++) std::memcpy(g1k.data() + i * HBH_G1_BYTES, e->g1k.data(), HBH_G1_BYTES);
+  }
+  // e(G1K, W) == e(U, Q_bp): sides as Engine.verify_ciphertexts_bp's (P1 = G1K, Q1 = W, P2 = U, Q2 = Q)
+  if (!device) {
+    std::vector<uint8_t> q(n * HBH_G2_BYTES);
+    rc = hbh_hash_g1_g2_bp(n, u, data, offsets, q.data(), 0);
+    if (rc) return fail(rc, hbh_host_last_error());
+    return run_pairing_eq_host(e, n, g1k.data(), w, n, nullptr, u, q.data(), n, nullptr, v);
+  }
+  std::vector<uint8_t> seeds(n * 32), state(n), fixed;
+  hbh__hash_seeds(n, u, data, offsets, seeds.data());
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  // the Q_bp are written straight into the Q2 staging buffer of the pairing path and stay in HBM
+  HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
+  HBH_CHECK(e->in_q2.ensure(n * HBH_G2_BYTES));
+  rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->in_q2.p, hbl::HASH_FORM_BP);
+  if (rc) return rc;
+  HBH_CHECK(upload(s, e->in_p1, g1k.data(), n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_q1, w, n * HBH_G2_BYTES));
+  HBH_CHECK(upload(s, e->in_p2, u, n * HBH_G1_BYTES));
+  HBH_CHECK(e->out_v.ensure(n));
+  HBH_CHECK(download(s, state.data(), e->hash_state, n));
+  HBH_CHECK(hipStreamSynchronize(s));
+  const std::vector<uint32_t> left = hash_leftovers(state);
+  if (!left.empty()) {  // host-hashed, then patched into the table
+    fixed.resize(n * HBH_G2_BYTES);
+    hbh__hash_g2_bp_seeds(left.size(), left.data(), seeds.data(), fixed.data());
+    for (uint32_t i : left)
+      HBH_CHECK(h2d(s, (uint8_t*)e->in_q2.p + (size_t)i * HBH_G2_BYTES, fixed.data() + (size_t)i * HBH_G2_BYTES,
+                    HBH_G2_BYTES));
+  }
+  rc = run_pairing_sides(e, s, n, {e->in_p1.p, e->in_q1.p, nullptr, nullptr, nullptr, n},
+                         {e->in_p2.p, e->in_q2.p, nullptr, nullptr, nullptr, n}, Resident(), 1, (uint8_t*)e->out_v.p);
+  if (rc) return rc;
+  HBH_CHECK(download(s, v, e->out_v, n));
+  return call.finish();
+}
+
+int hbh_engine_encrypt(hbh_engine* e, size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data,
+                       const size_t* offsets, const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, uint8_t* w_out) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!pks || !nonces || !u_out || !w_out) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_msgs(n, data, offsets);
+  if (rc) return rc;
+  if (offsets[n] && !v_out) return fail(HBH_ERR_ARG, "null pointer");
+  bool device;
+  {
+    std::lock_guard<std::mutex> lk(e->mu);
+    device = hash_on_device(e, n);
+  }
+  if (!device) {
+    rc = hbh_encrypt(n, pks, pk_per_item, data, offsets, nonces, u_out, v_out, w_out, 0);
+    return rc ? fail(rc, hbh_host_last_error()) : HBH_OK;
+  }
+  // U, V and W on the host workers; between them only the seeds sha3(hash_g1_g2's message of the public
+  // (U, V)) go to the device and the Q_bp come back.  Nonces, pk r and plaintexts stay in host memory.
+  rc = hbh_encrypt_uv(n, pks, pk_per_item, data, offsets, nonces, u_out, v_out, 0);
+  if (rc) return fail(rc, hbh_host_last_error());
+  std::vector<uint8_t> seeds(n * 32), q(n * HBH_G2_BYTES);
+  hbh__hash_seeds(n, u_out, v_out, offsets, seeds.data());
+  rc = hash_seeds_device(e, n, seeds, hbl::HASH_FORM_BP, q.data());
+  if (rc) return rc;
+  rc = hbh_encrypt_w(n, q.data(), nonces, w_out, 0);
+  return rc ? fail(rc, hbh_host_last_error()) : HBH_OK;
 }
 
 }  // extern "C"

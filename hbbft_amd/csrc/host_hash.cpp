@@ -752,6 +752,71 @@ int host_fail(int code, const char* msg) {
 }
 // scalar (32 B LE) -> 4 limbs
 void scalar_limbs(const uint8_t* s, uint64_t* k) { memcpy(k, s, 32); }
+// The key handling of hbh_encrypt / hbh_encrypt_uv: one key, or one per item; a key that encrypts at
+// least COMB_MIN items of the call gets a comb, the others go through GLV.
+struct EncryptKeys {
+  static constexpr size_t COMB_MIN = 16;
+  std::vector<uint32_t> key_of;
+  std::vector<hh::Jac<hh::Fq>> key_pt;
+  std::vector<std::vector<hh::Aff<hh::Fq>>> combs;
+
+  // false: a key coordinate >= p
+  bool prepare(size_t n, const uint8_t* pks, int pk_per_item, int threads) {
+    hh::g1_comb();  // build the fixed-base table before the workers share it
+    key_of.assign(n, 0);
+    std::vector<const uint8_t*> keys;
+    if (pk_per_item) {
+      std::unordered_map<std::string, uint32_t> seen;
+      for (size_t i = 0; i < n; i++) {
+        const uint8_t* k = pks + i * HBH_G1_BYTES;
+        auto it = seen.emplace(std::string((const char*)k, HBH_G1_BYTES), (uint32_t)keys.size());
+        if (it.second) keys.push_back(k);
+        key_of[i] = it.first->second;
+      }
+    } else {
+      keys.push_back(pks);
+    }
+    std::vector<size_t> uses(keys.size(), 0);
+    for (size_t i = 0; i < n; i++) uses[key_of[i]]++;
+    key_pt.resize(keys.size());
+    combs.resize(keys.size());
+    std::atomic<int> bad(0);
+    hh::parallel_for(keys.size(), threads, [&](size_t j) {
+      if (!hh::g1_from_abi(keys[j], key_pt[j])) {
+        bad = 1;
+        return;
+      }
+      if (uses[j] >= COMB_MIN) combs[j] = hh::comb4_build(key_pt[j]);
+    });
+    return !bad;
+  }
+
+  // item i: U = g1 r (g1's comb) and pk r (the key's comb, or GLV), made affine with one inversion;
+  // V = msg xor stream(pk r)
+  void uv(size_t i, const uint8_t* nonce, const uint8_t* msg, size_t len, uint8_t* u, uint8_t* v) const {
+    const uint32_t kj = key_of[i];
+    uint64_t r[4];
+    scalar_limbs(nonce, r);
+    hh::reduce_r(r);
+    const hh::Jac<hh::Fq> jp[2] = {hh::g1_mul_gen(r),
+                                   combs[kj].empty() ? hh::g1_mul_glv(key_pt[kj], r) : hh::comb4_mul(combs[kj], r)};
+    hh::Aff<hh::Fq> ap[2];
+    hh::jac_batch_affine(jp, ap, 2);
+    hh::g1_aff_to_abi(ap[0], u);
+    uint8_t g[HBH_G1_BYTES];
+    hh::g1_aff_to_abi(ap[1], g);
+    hh::xor_with_hash(g, msg, len, v);
+  }
+};
+
+// W = [KCOF r mod r] Q_bp for the nonce r (32 B LE, any 256-bit integer): one GLS multiplication
+void encrypt_w(const hh::Jac<hh::Fq2>& qbp, const uint8_t* nonce, uint8_t* w) {
+  uint64_t r[4], kr[4];
+  scalar_limbs(nonce, r);
+  hh::reduce_r(r);
+  hh::fr_mul(hh::KCOF, r, kr);
+  hh::g2_to_abi(hh::g2_mul_gls(qbp, kr), w);
+}
 }  // namespace
 
 extern "C" {
@@ -911,56 +976,46 @@ int hbh_encrypt(size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* da
     return host_fail(HBH_ERR_ARG, "null pointer");
   for (size_t i = 0; i < n; i++)
     if (offsets[i + 1] < offsets[i]) return host_fail(HBH_ERR_ARG, "offsets not ascending");
-  hh::g1_comb();  // build the fixed-base table before the workers share it
-  // keys: one, or one per item; a key that encrypts at least COMB_MIN items of this call gets a comb
-  const size_t COMB_MIN = 16;
-  std::vector<uint32_t> key_of(n, 0);
-  std::vector<const uint8_t*> keys;
-  if (pk_per_item) {
-    std::unordered_map<std::string, uint32_t> seen;
-    for (size_t i = 0; i < n; i++) {
-      const uint8_t* k = pks + i * HBH_G1_BYTES;
-      auto it = seen.emplace(std::string((const char*)k, HBH_G1_BYTES), (uint32_t)keys.size());
-      if (it.second) keys.push_back(k);
-      key_of[i] = it.first->second;
-    }
-  } else {
-    keys.push_back(pks);
-  }
-  std::vector<size_t> uses(keys.size(), 0);
-  for (size_t i = 0; i < n; i++) uses[key_of[i]]++;
-  std::vector<hh::Jac<hh::Fq>> key_pt(keys.size());
-  std::vector<std::vector<hh::Aff<hh::Fq>>> combs(keys.size());
+  EncryptKeys keys;
+  if (!keys.prepare(n, pks, pk_per_item, threads)) return host_fail(HBH_ERR_ARG, "coordinate >= p");
+  hh::parallel_for(n, threads, [&](size_t i) {
+    const size_t len = offsets[i + 1] - offsets[i];
+    uint8_t* u = u_out + i * HBH_G1_BYTES;
+    keys.uv(i, nonces + i * 32, data + offsets[i], len, u, v_out + offsets[i]);
+    // W = hash_g1_g2(U, V) r = [KCOF] Q_bp r = [KCOF r mod r] Q_bp: one GLS multiplication
+    const std::vector<uint8_t> m = hh::g1_g2_msg(u, v_out + offsets[i], len);
+    encrypt_w(hh::hash_g2_bp(m.data(), m.size()), nonces + i * 32, w_out + i * HBH_G2_BYTES);
+  });
+  return HBH_OK;
+}
+
+int hbh_encrypt_uv(size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data, const size_t* offsets,
+                   const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, int threads) {
+  if (n == 0) return HBH_OK;
+  if (!pks || !offsets || !nonces || !u_out || (offsets[n] && (!data || !v_out)))
+    return host_fail(HBH_ERR_ARG, "null pointer");
+  for (size_t i = 0; i < n; i++)
+    if (offsets[i + 1] < offsets[i]) return host_fail(HBH_ERR_ARG, "offsets not ascending");
+  EncryptKeys keys;
+  if (!keys.prepare(n, pks, pk_per_item, threads)) return host_fail(HBH_ERR_ARG, "coordinate >= p");
+  hh::parallel_for(n, threads, [&](size_t i) {
+    keys.uv(i, nonces + i * 32, data + offsets[i], offsets[i + 1] - offsets[i], u_out + i * HBH_G1_BYTES,
+            v_out + offsets[i]);
+  });
+  return HBH_OK;
+}
+
+int hbh_encrypt_w(size_t n, const uint8_t* qbp, const uint8_t* nonces, uint8_t* w_out, int threads) {
+  if (n == 0) return HBH_OK;
+  if (!qbp || !nonces || !w_out) return host_fail(HBH_ERR_ARG, "null pointer");
   std::atomic<int> bad(0);
-  hh::parallel_for(keys.size(), threads, [&](size_t j) {
-    if (!hh::g1_from_abi(keys[j], key_pt[j])) {
+  hh::parallel_for(n, threads, [&](size_t i) {
+    hh::Jac<hh::Fq2> q;
+    if (!hh::g2_from_abi(qbp + i * HBH_G2_BYTES, q)) {
       bad = 1;
       return;
     }
-    if (uses[j] >= COMB_MIN) combs[j] = hh::comb4_build(key_pt[j]);
-  });
-  if (bad) return host_fail(HBH_ERR_ARG, "coordinate >= p");
-  hh::parallel_for(n, threads, [&](size_t i) {
-    const uint32_t kj = key_of[i];
-    uint64_t r[4];
-    scalar_limbs(nonces + i * 32, r);
-    hh::reduce_r(r);
-    // U = g1 r (g1's comb) and pk r (the key's comb, or GLV), made affine with one inversion
-    const hh::Jac<hh::Fq> jp[2] = {hh::g1_mul_gen(r),
-                                   combs[kj].empty() ? hh::g1_mul_glv(key_pt[kj], r) : hh::comb4_mul(combs[kj], r)};
-    hh::Aff<hh::Fq> ap[2];
-    hh::jac_batch_affine(jp, ap, 2);
-    uint8_t* u = u_out + i * HBH_G1_BYTES;
-    hh::g1_aff_to_abi(ap[0], u);
-    uint8_t g[HBH_G1_BYTES];
-    hh::g1_aff_to_abi(ap[1], g);
-    const size_t len = offsets[i + 1] - offsets[i];
-    hh::xor_with_hash(g, data + offsets[i], len, v_out + offsets[i]);  // V = msg xor stream
-    // W = hash_g1_g2(U, V) r = [KCOF] Q_bp r = [KCOF r mod r] Q_bp: one GLS multiplication
-    const std::vector<uint8_t> m = hh::g1_g2_msg(u, v_out + offsets[i], len);
-    uint64_t kr[4];
-    hh::fr_mul(hh::KCOF, r, kr);
-    hh::g2_to_abi(hh::g2_mul_gls(hh::hash_g2_bp(m.data(), m.size()), kr), w_out + i * HBH_G2_BYTES);
+    encrypt_w(q, nonces + i * 32, w_out + i * HBH_G2_BYTES);  // Q = O (all zero) gives W = O (all zero)
   });
   return bad ? host_fail(HBH_ERR_ARG, "coordinate >= p") : HBH_OK;
 }
@@ -1029,5 +1084,13 @@ extern "C" void hbh__hash_g2_seeds(size_t n, const uint32_t* which, const uint8_
     const size_t i = which[k];
     hh::ChaChaRng rng(seeds + i * 32);
     hh::g2_to_abi(hh::g2_mul_gls(hh::g2_rand_bp(rng), hh::KCOF), out + i * HBH_G2_BYTES);
+  });
+}
+// the same for the Q form (k_hash_clear_bp): out[which[k]] = Q_bp of that seed, hbh_hash_g1_g2_bp's bytes
+extern "C" void hbh__hash_g2_bp_seeds(size_t n, const uint32_t* which, const uint8_t* seeds, uint8_t* out) {
+  hh::parallel_for(n, 0, [&](size_t k) {
+    const size_t i = which[k];
+    hh::ChaChaRng rng(seeds + i * 32);
+    hh::g2_to_abi(hh::g2_rand_bp(rng), out + i * HBH_G2_BYTES);
   });
 }

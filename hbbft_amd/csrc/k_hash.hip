@@ -12,6 +12,9 @@
 //                  compacted worklist instead of a per-lane loop: half the candidates fail, and a wave
 //                  that loops waits for its unluckiest lane (12 candidates among 2,000 test messages).
 //   k_hash_clear   one lane per sampled point: h2 (x, y) to affine ABI words with one inversion.
+//   k_hash_clear_bp  the Q form of the same body: it stops at the Budroni-Pintore image Q_bp (h2 (x, y) =
+//                  [KCOF] Q_bp), the bytes of the host stage's hbh_hash_g1_g2_bp, for callers that fold
+//                  [KCOF] into a pairing side or a scalar (Ciphertext::verify, encrypt's W).
 //
 // Outputs are keyed by message index, so the order in which lanes append to a worklist does not matter.
 // Every loop is bounded: the launcher runs a fixed number of rounds, gen_fq draws at most 64 times, and a
@@ -136,9 +139,11 @@ __device__ __forceinline__ Jac<Fp2> cofactor_bp(const Jac<Fp2>& p) {
   return jac_add(t3, jac_neg(p));
 }
 
-__global__ void __launch_bounds__(64) k_hash_clear(int n, const uint32_t* __restrict__ xy, uint8_t* __restrict__ state,
-                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ retry_list,
-                                                   uint32_t* __restrict__ retry_count) {
+// FULL: out = h2 (x, y) = [KCOF] Q_bp (hash_g2's bytes); otherwise out = Q_bp
+template <bool FULL>
+__device__ __forceinline__ void hash_clear(int n, const uint32_t* __restrict__ xy, uint8_t* __restrict__ state,
+                                           uint32_t* __restrict__ out, uint32_t* __restrict__ retry_list,
+                                           uint32_t* __restrict__ retry_count) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
   const uint8_t st = state[i];
@@ -171,8 +176,28 @@ __global__ void __launch_bounds__(64) k_hash_clear(int n, const uint32_t* __rest
     }
     return;
   }
-  g2_jac_to_words(kcof_mul(q), o);
+  if (FULL)
+    g2_jac_to_words(kcof_mul(q), o);
+  else
+    g2_jac_to_words(q, o);
   state[i] = hbl::HASH_DONE;
+}
+
+__global__ void __launch_bounds__(64) k_hash_clear(int n, const uint32_t* __restrict__ xy, uint8_t* __restrict__ state,
+                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ retry_list,
+                                                   uint32_t* __restrict__ retry_count) {
+  hash_clear<true>(n, xy, state, out, retry_list, retry_count);
+}
+
+// The Q form saves kcof_mul's 62 doublings + 27 additions per message, not registers: cofactor_bp's second
+// chain keeps p, t1, t3, the chain's base and its accumulator live (five Jacobian points, 420 words) beside
+// jac_add's temporaries, so this instantiation fills the 512-register budget of one wave per SIMD as the
+// full form does (profiles/r15/README.md has both reports).
+__global__ void __launch_bounds__(64) k_hash_clear_bp(int n, const uint32_t* __restrict__ xy,
+                                                      uint8_t* __restrict__ state, uint32_t* __restrict__ out,
+                                                      uint32_t* __restrict__ retry_list,
+                                                      uint32_t* __restrict__ retry_count) {
+  hash_clear<false>(n, xy, state, out, retry_list, retry_count);
 }
 
 }  // namespace hb
@@ -203,8 +228,10 @@ size_t hash_work_bytes(size_t n, int rounds) {
   return (hash_count_words(rounds) + (2 + (size_t)hb::XY_WORDS + 3) * n) * sizeof(uint32_t);
 }
 
-hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out) {
+hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out,
+                   HashForm form) {
   if (n <= 0) return hipSuccess;
+  const auto clear = form == HASH_FORM_BP ? hb::k_hash_clear_bp : hb::k_hash_clear;
   const HashWork w = hash_carve(work, (size_t)n, rounds);
   hipError_t err = hipMemsetAsync(w.counts, 0, (size_t)((uint8_t*)w.xy - (uint8_t*)w.counts), s);
   if (err != hipSuccess) return err;
@@ -218,7 +245,7 @@ hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void*
     hipLaunchKernelGGL(hb::k_hash_sample, grid, block, 0, s, n, k ? w.counts + k : nullptr, k ? w.list[k & 1] : nullptr,
                        seeds, w.pos, w.xy, state, w.list[(k + 1) & 1], w.counts + k + 1);
   uint32_t* rc = w.counts + rounds + 1;
-  hipLaunchKernelGGL(hb::k_hash_clear, grid, block, 0, s, n, w.xy, state, (uint32_t*)out, w.retry, rc);
+  hipLaunchKernelGGL(clear, grid, block, 0, s, n, w.xy, state, (uint32_t*)out, w.retry, rc);
   // messages whose multiple was O (none in practice): a short series of rounds and a second clearing,
   // which also zeroes whatever is still unresolved
   const uint32_t* cnt = rc;
@@ -229,7 +256,7 @@ hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void*
     cnt = rc + 1 + k;
     lst = w.list[k & 1];
   }
-  hipLaunchKernelGGL(hb::k_hash_clear, grid, block, 0, s, n, w.xy, state, (uint32_t*)out, (uint32_t*)nullptr,
+  hipLaunchKernelGGL(clear, grid, block, 0, s, n, w.xy, state, (uint32_t*)out, (uint32_t*)nullptr,
                      (uint32_t*)nullptr);
   return hipGetLastError();
 }

@@ -161,8 +161,13 @@ hipError_t commit_eval(hipStream_t s, int n, int t, const void* commits, const u
 // next candidate x of every message that has no point yet, then the cofactor multiplication.  A message
 // that needed more candidates than rounds ends with state != HASH_DONE and an all-zero point.
 // Asynchronous on s; work = hash_work_bytes(n, rounds) bytes.
+// form: HASH_FORM_FULL writes hash_g2's point h2 (x, y); HASH_FORM_BP stops at the Budroni-Pintore image
+// Q_bp (h2 (x, y) = [KCOF] Q_bp, the bytes of hbh_hash_g1_g2_bp) and skips the [KCOF] chain.  Both forms
+// share the sampler, the work layout and the state bytes.
 constexpr uint8_t HASH_PENDING = 0, HASH_SAMPLED = 1, HASH_DONE = 2, HASH_FAILED = 3;
+enum HashForm { HASH_FORM_FULL = 0, HASH_FORM_BP = 1 };
 size_t hash_work_bytes(size_t n, int rounds);
-hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out);
+hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out,
+                   HashForm form = HASH_FORM_FULL);
 
 }  // namespace hbl

@@ -66,6 +66,8 @@ class DhbKeyGen:
         self.secret_key = secret_key
         self.public_keys = dict(public_keys)
         self.device_hash = device_hash  # batch checks hash their messages in the engine (verify_signed)
+        # key_gen is made by the caller: SyncKeyGen.new(..., device_hash=True) gives its Ciphertext::verify
+        # and encryption batches the same treatment (this flag does not reach into it)
         self.key_gen = key_gen
         self.candidate_keys = dict(candidate_keys or {})
         self.is_validator = is_validator

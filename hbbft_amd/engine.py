@@ -166,6 +166,63 @@ class Engine:
         raw = bytes(out)
         return [raw[i * G2_BYTES:(i + 1) * G2_BYTES] for i in range(n)]
 
+    def hash_g1_g2_bp(self, us, vs):
+        """Q_i with hash_g1_g2(U_i, V_i) = [KCOF] Q_i, the bytes of hoststage.hash_g1_g2_bp
+        (hbh_engine_hash_g1_g2_bp: the Q form of the device hash, without the [KCOF] chain)."""
+        from .hoststage import _concat
+        n = len(us)
+        if len(vs) != n:
+            raise ValueError("us / vs length mismatch")
+        data, offs = _concat(vs)
+        out = (ctypes.c_uint8 * max(n * G2_BYTES, 1))()
+        keep = [buf(_join(us, G1_BYTES) or b"\0"), buf(data or b"\0")]
+        check(self._l.hbh_engine_hash_g1_g2_bp(self._h, n, keep[0][1], keep[1][1],
+                                               offs.ctypes.data_as(ctypes.c_void_p), ctypes.cast(out, ctypes.c_void_p)))
+        raw = bytes(out)
+        return [raw[i * G2_BYTES:(i + 1) * G2_BYTES] for i in range(n)]
+
+    def verify_ciphertexts_uv(self, us, vs, ws):
+        """Ciphertext::verify batch from the ciphertexts themselves (hbh_verify_ciphertexts_uv): the
+        verdicts of verify_ciphertexts_bp(us, ws, hoststage.hash_g1_g2_bp(us, vs)) with the hash computed
+        inside the call -- on the device for large batches (set_hash_impl), where it never leaves HBM."""
+        from .hoststage import _concat
+        ub, wb = _join(us, G1_BYTES), _join(ws, G2_BYTES)
+        n = len(ub) // G1_BYTES
+        if len(wb) // G2_BYTES != n or len(vs) != n:
+            raise ValueError("us / vs / ws length mismatch")
+        data, offs = _concat(vs)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        keep = [buf(ub or b"\0"), buf(data or b"\0"), buf(wb or b"\0")]
+        check(self._l.hbh_verify_ciphertexts_uv(self._h, n, keep[0][1], keep[1][1],
+                                                offs.ctypes.data_as(ctypes.c_void_p), keep[2][1],
+                                                ctypes.cast(out, ctypes.c_void_p)))
+        return bytes(out)[:n]
+
+    def encrypt(self, pks, msgs, nonces):
+        """PublicKey::encrypt_with_rng per message with caller-drawn nonces, the bytes of
+        hoststage.encrypt: [(U, V, W)] (hbh_engine_encrypt).  For large batches (set_hash_impl) the hash of
+        the public (U, V) runs on the device; nonces, pk r and plaintexts never leave the host."""
+        from .hoststage import _concat
+        n = len(msgs)
+        if len(nonces) != n:
+            raise ValueError("msgs / nonces length mismatch")
+        per_item = len(pks) != 1
+        if per_item and len(pks) != n:
+            raise ValueError("pks must hold one key or one per message")
+        data, offs = _concat(msgs)
+        keep = [buf(_join(pks, G1_BYTES)), buf(data or b"\0"),
+                buf(b"".join(int(r).to_bytes(32, "little") for r in nonces) or b"\0")]
+        ou = (ctypes.c_uint8 * max(n * G1_BYTES, 1))()
+        ov = (ctypes.c_uint8 * max(len(data), 1))()
+        ow = (ctypes.c_uint8 * max(n * G2_BYTES, 1))()
+        vp = ctypes.c_void_p
+        check(self._l.hbh_engine_encrypt(self._h, n, keep[0][1], 1 if per_item else 0, keep[1][1],
+                                         offs.ctypes.data_as(vp), keep[2][1], ctypes.cast(ou, vp), ctypes.cast(ov, vp),
+                                         ctypes.cast(ow, vp)))
+        raw_u, raw_v, raw_w = bytes(ou), bytes(ov), bytes(ow)
+        return [(raw_u[i * G1_BYTES:(i + 1) * G1_BYTES], raw_v[int(offs[i]):int(offs[i + 1])],
+                 raw_w[i * G2_BYTES:(i + 1) * G2_BYTES]) for i in range(n)]
+
     def hash_g2_dev(self, stream, n, d_seeds, d_out):
         """Device-pointer form (hbh_hash_g2_dev): n 32-byte seeds (sha3_256 of each message) in HBM ->
         n ABI G2 points in HBM, asynchronous.  A message that needed more candidates than the sampler's
@@ -175,7 +232,8 @@ class Engine:
 
     def set_hash_impl(self, impl):
         """HBH_HASH_*: 0 = auto (default: the device from AUTO_HASH_DEVICE_MIN messages per call), 1 = the
-        host stage, 2 = the device.  Governs hash_g2, hash_g1_g2 and verify_signed; same bytes either way."""
+        host stage, 2 = the device.  Governs hash_g2, hash_g1_g2, hash_g1_g2_bp, verify_signed,
+        verify_ciphertexts_uv and encrypt; same bytes and verdicts either way."""
         check(self._l.hbh_engine_set_hash_impl(self._h, int(impl)))
 
     def dbg_set_hash_rounds(self, rounds):

@@ -195,6 +195,43 @@ def encrypt(pks, msgs, nonces, threads=0):
     return [(us[i], raw_v[int(offs[i]):int(offs[i + 1])], ws[i]) for i in range(n)]
 
 
+def encrypt_uv(pks, msgs, nonces, threads=0):
+    """The first half of encrypt (hbh_encrypt_uv): [(U, V)] with U = g1 r, V = msg xor stream(pk r).  The
+    caller hashes the public (U, V) to Q_bp (hash_g1_g2_bp, or Engine.hash_g1_g2_bp) and finishes with
+    encrypt_w."""
+    l = _lib.lib()
+    n = len(msgs)
+    if len(nonces) != n:
+        raise ValueError("msgs / nonces length mismatch")
+    per_item = len(pks) != 1
+    if per_item and len(pks) != n:
+        raise ValueError("pks must hold one key or one per message")
+    data, offs = _concat(msgs)
+    kk, pk = _buf(b"".join(bytes(x) for x in pks))
+    kd, pd = _buf(data)
+    kn, pn = _buf(b"".join(int(r).to_bytes(32, "little") for r in nonces))
+    ou, pu = _out(n * G1_BYTES)
+    ov, pv = _out(len(data))
+    check_host(l.hbh_encrypt_uv(n, pk, 1 if per_item else 0, pd, offs.ctypes.data_as(ctypes.c_void_p), pn, pu, pv,
+                                int(threads)))
+    raw_v = bytes(ov)[:len(data)]
+    us = _split(bytes(ou), G1_BYTES, n)
+    return [(us[i], raw_v[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
+
+
+def encrypt_w(qbps, nonces, threads=0):
+    """The second half of encrypt (hbh_encrypt_w): W_i = [KCOF r_i mod r] Q_i for Q_i = Q_bp of (U_i, V_i);
+    an all-zero Q_i gives the all-zero W_i."""
+    n = len(qbps)
+    if len(nonces) != n:
+        raise ValueError("qbps / nonces length mismatch")
+    kq, pq = _buf(b"".join(bytes(q) for q in qbps))
+    kn, pn = _buf(b"".join(int(r).to_bytes(32, "little") for r in nonces))
+    o, po = _out(n * G2_BYTES)
+    check_host(_lib.lib().hbh_encrypt_w(n, pq, pn, po, int(threads)))
+    return _split(bytes(o), G2_BYTES, n)
+
+
 def fr_poly_eval(polys, xs, threads=0):
     """Poly::evaluate over Fr (hbh_fr_poly_eval): [[poly(x) for x in xs] for poly in polys]; every
     polynomial is a coefficient list (constant term first) of one common length, coefficients < r."""

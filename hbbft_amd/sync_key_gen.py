@@ -6,7 +6,9 @@ Same message types (``Part``, ``Ack``), outcomes (``PartOutcome`` / ``AckOutcome
 
   GPU (engine, public data)   BivarCommitment::row (hbh_bivar_row), Poly::commitment (hbh_g1_mul_gen of
                               g1), BivarPoly::commitment, Ciphertext::verify (hbh_verify_ciphertexts),
-                              BivarCommitment::evaluate == g1 * val (hbh_bivar_ack_check)
+                              BivarCommitment::evaluate == g1 * val (hbh_bivar_ack_check); with
+                              device_hash=True also hash_g1_g2 of the public (U, V) of large batches
+                              (hbh_verify_ciphertexts_uv, hbh_engine_encrypt)
   host (secrets, hashing)     SecretKey::decrypt's U * sk and XOR stream, encrypt_with_rng,
                               hash_g1_g2 (hbbft_amd.hoststage, csrc/host_hash.cpp); Fr arithmetic
 
@@ -207,15 +209,19 @@ class PublicKeySet:
 
 
 # ------------------------------------------------------------------ crypto batches
-def _decrypt_batch(engine, sec_key, cts, threads=0):
+def _decrypt_batch(engine, sec_key, cts, threads=0, device_hash=False):
     """SecretKey::decrypt for a list of ciphertexts: None where Ciphertext::verify fails
-    (sync_key_gen.rs:503-506, 535-538)."""
+    (sync_key_gen.rs:503-506, 535-538).  device_hash: Ciphertext::verify from (U, V, W) in one engine
+    call (hbh_verify_ciphertexts_uv), which hashes large batches on the device; the same verdicts."""
     if not cts:
         return []
     # Ciphertext::verify in its Q form (hbh_hash_g1_g2_bp): the same verdicts without the final
     # G2 scalar multiplication of each hash
-    qbp = hoststage.hash_g1_g2_bp([c.u for c in cts], [c.v for c in cts], threads)
-    ok = engine.verify_ciphertexts_bp([c.u for c in cts], [c.w for c in cts], qbp)
+    if device_hash:
+        ok = engine.verify_ciphertexts_uv([c.u for c in cts], [c.v for c in cts], [c.w for c in cts])
+    else:
+        qbp = hoststage.hash_g1_g2_bp([c.u for c in cts], [c.v for c in cts], threads)
+        ok = engine.verify_ciphertexts_bp([c.u for c in cts], [c.w for c in cts], qbp)
     good = [k for k, v in enumerate(ok) if v]
     out = [None] * len(cts)
     if good:
@@ -226,16 +232,23 @@ def _decrypt_batch(engine, sec_key, cts, threads=0):
     return out
 
 
-def _encrypt_batch(pks, payloads, rng, threads=0):
-    """PublicKey::encrypt_with_rng per (pk, payload); nonces drawn from the caller's rng."""
+def _encrypt_batch(pks, payloads, rng, threads=0, engine=None):
+    """PublicKey::encrypt_with_rng per (pk, payload); nonces drawn from the caller's rng.  With an engine
+    the hash of each public (U, V) may run on the device (hbh_engine_encrypt): the same nonces in the same
+    order and the same bytes; nonces, pk r and payloads stay on the host either way."""
     nonces = [rng.randrange(1, R_ORDER) for _ in payloads]
+    if engine is not None:
+        return [Ciphertext(u, v, w) for (u, v, w) in engine.encrypt(pks, payloads, nonces)]
     return [Ciphertext(u, v, w) for (u, v, w) in hoststage.encrypt(pks, payloads, nonces, threads)]
 
 
 # ------------------------------------------------------------------ SyncKeyGen
 class SyncKeyGen:
-    def __init__(self, our_id, sec_key, pub_keys, threshold, engine, threads=0):
-        """sec_key: this node's encryption secret key (Fr int); pub_keys: {node_id: G1 ABI}."""
+    def __init__(self, our_id, sec_key, pub_keys, threshold, engine, threads=0, device_hash=False):
+        """sec_key: this node's encryption secret key (Fr int); pub_keys: {node_id: G1 ABI}.
+        device_hash: take hash_g1_g2 of the public (U, V) of every ciphertext this instance checks or
+        makes through the engine (verify_ciphertexts_uv, Engine.encrypt), which hashes large batches on
+        the device (Engine.set_hash_impl); same messages, outcomes and keys."""
         self.our_id = our_id
         self.sec_key = sec_key
         self.pub_keys = dict(sorted(pub_keys.items()))
@@ -245,6 +258,7 @@ class SyncKeyGen:
         self.parts = {}
         self.engine = engine
         self.threads = threads
+        self.device_hash = bool(device_hash)
         self._sets = {}  # degree -> CommitSet: every Part's commitment uploaded to HBM once
 
     def _commit_set(self, degree):
@@ -254,12 +268,12 @@ class SyncKeyGen:
         return cs
 
     @classmethod
-    def new(cls, our_id, sec_key, pub_keys, threshold, engine, rng=None, threads=0):
+    def new(cls, our_id, sec_key, pub_keys, threshold, engine, rng=None, threads=0, device_hash=False):
         """SyncKeyGen::new (sync_key_gen.rs:323-357): the instance and our Part (None for an
         observer).  BivarPoly::random(threshold), commitment on the GPU, one encrypted row per
         node on the host."""
         rng = rng or random.SystemRandom()
-        kg = cls(our_id, sec_key, pub_keys, threshold, engine, threads)
+        kg = cls(our_id, sec_key, pub_keys, threshold, engine, threads, device_hash)
         if kg.our_idx is None:
             return kg, None
         t = threshold
@@ -272,7 +286,8 @@ class SyncKeyGen:
         ev = hoststage.fr_poly_eval([[coeffs[coeff_pos(a, b)] for b in range(t + 1)] for a in range(t + 1)], xs,
                                     threads)
         rows = [[ev[a][i] for a in range(t + 1)] for i in range(len(xs))]
-        cts = _encrypt_batch(list(kg.pub_keys.values()), [ser_row(r) for r in rows], rng, threads)
+        cts = _encrypt_batch(list(kg.pub_keys.values()), [ser_row(r) for r in rows], rng, threads,
+                             engine if kg.device_hash else None)
         return kg, Part(t, commit, cts)
 
     def public_keys(self):
@@ -335,7 +350,8 @@ class SyncKeyGen:
                 got = cs.rows([first + k for k in range(len(js))], [x] * len(js))
                 for j, r in zip(js, got):
                     commit_rows[j] = r
-            plain = _decrypt_batch(self.engine, self.sec_key, [p.rows[self.our_idx] for _, p, _ in new], self.threads)
+            plain = _decrypt_batch(self.engine, self.sec_key, [p.rows[self.our_idx] for _, p, _ in new], self.threads,
+                                   self.device_hash)
             polys = [de_row(b) if b is not None else None for b in plain]
             # Poly::commitment() only where the lengths agree: a row of another length can never
             # equal the commitment row (Commitment's derived PartialEq compares the vectors)
@@ -378,7 +394,8 @@ class SyncKeyGen:
             pks = list(self.pub_keys.values())
             vals = _eval_rows([row for _, _, row in ack_jobs], [i + 1 for i in range(n)], self.threads)
             payloads = [ser_val(v) for vs in vals for v in vs]
-            cts = _encrypt_batch([pk for _ in ack_jobs for pk in pks], payloads, rng, self.threads)
+            cts = _encrypt_batch([pk for _ in ack_jobs for pk in pks], payloads, rng, self.threads,
+                                 self.engine if self.device_hash else None)
             for j, (o, sidx, _) in enumerate(ack_jobs):
                 outs[o].ack = Ack(sidx, cts[j * n:(j + 1) * n])
         return outs
@@ -430,7 +447,8 @@ class SyncKeyGen:
         new = [p[1] for p in plan if p[0] == "new"]
         verdict = {}
         if new and self.our_idx is not None:
-            plain = _decrypt_batch(self.engine, self.sec_key, [a.values[self.our_idx] for _, a, _ in new], self.threads)
+            plain = _decrypt_batch(self.engine, self.sec_key, [a.values[self.our_idx] for _, a, _ in new], self.threads,
+                                   self.device_hash)
             vals = [de_val(b) if b is not None else None for b in plain]
             chk = [j for j, v in enumerate(vals) if v is not None]
             okmap = {}

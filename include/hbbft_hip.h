@@ -322,7 +322,8 @@ int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
 
 /* ---------------------------------------------------------------- hashing to G2 on the device
  * threshold_crypto hash_g2 / hash_g1_g2 for large batches of PUBLIC inputs (documents, signed messages,
- * the (U, V) of ciphertexts; hbh_encrypt and every secret-key operation keep the host stage).  SHA3 and
+ * the (U, V) of ciphertexts; every secret-key operation keeps the host stage, and so do the secret parts
+ * of encryption: of hbh_engine_encrypt only the SHA3 seeds of the public (U, V) reach the device).  SHA3 and
  * the message assembly run on the host (hbh_hash_g2's code and worker threads); the curve half --
  * sampling x from the seeded ChaCha20 stream, the square root, the sign choice and the cofactor
  * multiplication (csrc/hash_sample.hpp, k_hash.hip) -- runs on the GPU.  Output bytes are hbh_hash_g2's.
@@ -341,10 +342,25 @@ int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
  *     the hashes never leave HBM: they are the Q1 table of hbh_verify_pairing_eq under the identity map.
  *   hbh_engine_set_hash_impl: HBH_HASH_HOST (the host stage, hbh_hash_g2's workers), HBH_HASH_DEVICE, or
  *     HBH_HASH_AUTO (the default): DEVICE for calls of at least HBH_AUTO_HASH_DEVICE_MIN messages (0:
- *     never), HOST below.  Governs the three host-pointer calls; same bytes and verdicts from either.
+ *     never), HOST below.  Governs every host-pointer call of this section; same bytes and verdicts from
+ *     either.
  *     Threshold: the smallest swept size from which DEVICE's median host-to-host time is below HOST's by
  *     more than both cells' min-max spread, at that and every larger swept size (profiles/r14/README.md,
- *     tools/hash_bench.py).  Any other value returns HBH_ERR_ARG and changes nothing. */
+ *     tools/hash_bench.py).  Any other value returns HBH_ERR_ARG and changes nothing.
+ * The Q form (k_hash_clear_bp): the device stops at the Budroni-Pintore image Q_bp of the sampled point,
+ * hash_g1_g2(U, V) = [KCOF] Q_bp (hbh_hash_g1_g2_bp below), for the callers that fold [KCOF] into a pairing
+ * side or into a scalar they multiply by anyway.  HOST, DEVICE and AUTO as above; messages left after
+ * HBH_HASH_ROUNDS are hashed on the host stage and patched in.
+ *   hbh_engine_hash_g1_g2_bp: arguments and output bytes as hbh_hash_g1_g2_bp.
+ *   hbh_verify_ciphertexts_uv: Ciphertext::verify from the ciphertext itself (SecretKey::decrypt's check,
+ *     sync_key_gen.rs:503-506, 535-538): verdict[i] = e(G1K, W_i) == e(U_i, Q_bp(U_i, V_i)), the verdicts of
+ *     hbh_verify_ciphertexts bit for bit (U = O and W = O included).  u = n ABI G1 points, V_i =
+ *     data[offsets[i] .. offsets[i+1]), w = n ABI G2 points.  On the device form the hashes are written
+ *     into the Q2 table of the pairing check and never leave HBM.
+ *   hbh_engine_encrypt: hbh_encrypt's arguments (without threads) and bytes.  hbh_encrypt_uv on the host
+ *     workers, the seeds sha3_256(hash_g1_g2's message of (U_i, V_i)), Q_bp on the device, hbh_encrypt_w on
+ *     the host workers.  ONLY THOSE SEEDS CROSS TO THE DEVICE: they are hashes of the public wire message
+ *     (U, V).  The nonces, pk r, the plaintexts and the scalars KCOF r stay in host memory. */
 #define HBH_HASH_AUTO 0
 #define HBH_HASH_HOST 1
 #define HBH_HASH_DEVICE 2
@@ -357,6 +373,12 @@ int hbh_hash_g2_dev(hbh_engine* eng, void* stream, size_t n, const uint8_t* d_se
 int hbh_verify_signatures(hbh_engine* eng, size_t n, const uint8_t* pks, const uint8_t* sigs, const uint8_t* data,
                           const size_t* offsets, uint8_t* verdicts);
 int hbh_engine_set_hash_impl(hbh_engine* eng, int impl);
+int hbh_engine_hash_g1_g2_bp(hbh_engine* eng, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                             uint8_t* out);
+int hbh_verify_ciphertexts_uv(hbh_engine* eng, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
+                              const uint8_t* w, uint8_t* verdicts);
+int hbh_engine_encrypt(hbh_engine* eng, size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data,
+                       const size_t* offsets, const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, uint8_t* w_out);
 
 /* ---------------------------------------------------------------- host stage (CPU, no engine)
  * What the north star keeps on the host, batched over `threads` std::thread workers (0 = all
@@ -411,6 +433,17 @@ int hbh_host_g2_mul(size_t n, const uint8_t* pts, const uint8_t* scalars, uint8_
 int hbh_host_g1_add(size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out);
 int hbh_encrypt(size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data, const size_t* offsets,
                 const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, uint8_t* w_out, int threads);
+/* hbh_encrypt split at its hash, so that a caller can take Q_bp of (U, V) from any source between the
+ * halves (hbh_hash_g1_g2_bp, hbh_engine_hash_g1_g2_bp, a cache); hbh_engine_encrypt is that sequence.
+ *   hbh_encrypt_uv  U = g1 r and V = msg xor stream(pk r): hbh_encrypt's arguments, key handling (one key
+ *                   or one per item; a comb for a key with at least 16 items, GLV below) and U / V bytes
+ *   hbh_encrypt_w   W_i = [KCOF r_i mod r] Q_i by one GLS multiplication, Q_i = Q_bp of (U_i, V_i) (n ABI
+ *                   G2 points); an all-zero Q_i gives the all-zero W_i
+ * hbh_encrypt_uv, then Q = hbh_hash_g1_g2_bp(U, V), then hbh_encrypt_w gives hbh_encrypt's bytes.  (U, V)
+ * is the public wire message; the nonce r and pk r are secret and never leave these two calls. */
+int hbh_encrypt_uv(size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data, const size_t* offsets,
+                   const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, int threads);
+int hbh_encrypt_w(size_t n, const uint8_t* qbp, const uint8_t* nonces, uint8_t* w_out, int threads);
 int hbh_fr_poly_eval(size_t npoly, size_t ncoef, const uint8_t* coeffs, size_t npts, const uint64_t* xs, uint8_t* out,
                      int threads);
 
