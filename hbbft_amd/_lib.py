@@ -28,6 +28,10 @@ SIGNATURES = [
     ("hbh_verify_sig_shares", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_verify_dec_shares", _I, [_P, _SZ, _P, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_verify_ciphertexts", _I, [_P, _SZ, _P, _P, _P, _P]),
+    # grouped random-combination share checks (opt-in)
+    ("hbh_verify_sig_shares_grouped", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    ("hbh_verify_dec_shares_grouped", _I, [_P, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    ("hbh_dbg_group_sums", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_verify_pairing_eq_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_dbg_pairing", _I, [_P, _SZ, _P, _P, _P]),
     ("hbh_interpolate_g2", _I, [_P, _SZ, _I, _P, _P, _P, _P]),
@@ -118,6 +122,14 @@ AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPL
 HASH_AUTO, HASH_HOST, HASH_DEVICE = 0, 1, 2  # HBH_HASH_*
 HASH_ROUNDS = 32  # HBH_HASH_ROUNDS
 AUTO_HASH_DEVICE_MIN = 4096  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r14)
+GROUP_TILE = 128  # csrc/group_plan.hpp GROUP_TILE: items per tile of the grouped share checks' sums
+
+
+class GroupedStats(ctypes.Structure):
+    """hbh_grouped_stats"""
+    _fields_ = [("groups", ctypes.c_uint32), ("groups_passed", ctypes.c_uint32), ("singles", ctypes.c_uint32),
+                ("fallback_items", ctypes.c_uint32)]
+
 
 _lib = None
 

@@ -2112,3 +2112,244 @@ int hbh_verify_pairing_eq_set_dev(hbh_engine* e, void* stream, size_t n, const v
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- grouped random-combination share checks
+// Opt-in forms of hbh_verify_sig_shares / hbh_verify_dec_shares (include/hbbft_hip.h): the items that
+// share a table entry are settled by ONE pairing check on their random linear combination
+// (group_plan.hpp plans the groups, k_rlc.hip sums them); the items of a group whose check fails, and
+// the items alone in their group, take the per-share check, so every reported 0 is exact.
+#include <sys/random.h>
+
+#include "group_plan.hpp"
+
+namespace {
+
+constexpr size_t RLC_BYTES = 16;  // one scalar: 128 bits, little-endian
+
+bool rlc_is_zero(const uint8_t* r) {
+  uint8_t o = 0;
+  for (size_t k = 0; k < RLC_BYTES; k++) o |= r[k];
+  return o == 0;
+}
+
+int os_random(uint8_t* out, size_t bytes) {
+  while (bytes) {
+    const ssize_t got = getrandom(out, bytes < 256 ? bytes : 256, 0);  // <= 256 B is never cut short
+    if (got <= 0) return fail(HBH_ERR_DEVICE, "getrandom failed");
+    out += got;
+    bytes -= (size_t)got;
+  }
+  return HBH_OK;
+}
+
+// The n scalars of a call: the caller's (none may be zero), or n x 128 bits from the OS with a zero
+// draw replaced.
+int rlc_scalars(size_t n, const uint8_t* given, std::vector<uint8_t>& r) {
+  r.resize(n * RLC_BYTES);
+  if (given) {
+    std::memcpy(r.data(), given, r.size());
+    for (size_t i = 0; i < n; i++)
+      if (rlc_is_zero(&r[i * RLC_BYTES])) return fail(HBH_ERR_ARG, "zero scalar");
+    return HBH_OK;
+  }
+  int rc = os_random(r.data(), r.size());
+  for (size_t i = 0; i < n && !rc; i++)
+    while (!rc && rlc_is_zero(&r[i * RLC_BYTES])) rc = os_random(&r[i * RLC_BYTES], RLC_BYTES);
+  return rc;
+}
+
+// A plan's arrays and the scalars in device memory (e->in_b, e->in_a).  `packed` is the host image of
+// the plan arrays: the caller keeps it until the stream has synchronised.
+struct GroupDev {
+  const uint32_t *perm, *tile_off, *tile_len, *ctile, *centry, *scalars;
+  int ntile, ncomb, max_len;  // max_len: the longest tile
+};
+int upload_plan(hbh_engine* e, hipStream_t s, const GroupPlan& P, const std::vector<uint8_t>& scalars,
+                std::vector<uint32_t>& packed, GroupDev& d) {
+  const size_t n = P.perm.size(), nt = P.tile_off.size(), nc = P.comb.size();
+  if (n > (size_t)1 << 30) return fail(HBH_ERR_ARG, "batch too large");
+  packed.clear();
+  packed.insert(packed.end(), P.perm.begin(), P.perm.end());
+  packed.insert(packed.end(), P.tile_off.begin(), P.tile_off.end());
+  packed.insert(packed.end(), P.tile_len.begin(), P.tile_len.end());
+  packed.insert(packed.end(), P.ctile.begin(), P.ctile.end());
+  for (uint32_t g : P.comb) packed.push_back(P.entry[g]);
+  HBH_CHECK(upload(s, e->in_b, packed.data(), packed.size() * 4));
+  HBH_CHECK(upload(s, e->in_a, scalars.data(), scalars.size()));
+  d.perm = (const uint32_t*)e->in_b.p;
+  d.tile_off = d.perm + n;
+  d.tile_len = d.tile_off + nt;
+  d.ctile = d.tile_len + nt;
+  d.centry = d.ctile + nc + 1;
+  d.scalars = (const uint32_t*)e->in_a.p;
+  d.ntile = (int)nt;
+  d.ncomb = (int)nc;
+  d.max_len = 1;
+  for (uint32_t len : P.tile_len) d.max_len = std::max(d.max_len, (int)len);
+  return HBH_OK;
+}
+
+// out[c] = sum of r_i P_i over combined group c, for the n points d_pts (G1 or G2 ABI words); tile sums
+// in `region` (0 / 1) of e->work, which the caller sized for two G2 regions
+int launch_group_sums(hbh_engine* e, hipStream_t s, bool g2, size_t n, const void* d_pts, const GroupDev& d, int region,
+                      void* d_out) {
+  void* tiles = (uint8_t*)e->work.p + (size_t)region * d.ntile * hbl::group_tile_bytes(true);
+  HBH_CHECK((g2 ? hbl::group_sum_g2 : hbl::group_sum_g1)(s, d.ntile, (int)n, d.max_len, d_pts, d.scalars, d.perm,
+                                                        d.tile_off, d.tile_len, tiles));
+  HBH_CHECK((g2 ? hbl::group_join_g2 : hbl::group_join_g1)(s, d.ncomb, d.ctile, tiles, d_out));
+  return HBH_OK;
+}
+
+// The grouped check of one call.  a: the G1 points of side 1 (pk_i / D_i); b: sig_i (G2, dec = false)
+// or pk_i (G1, dec = true); q1: the table of side 1 (H / H_uv); q2: W (dec only).
+int run_grouped(hbh_engine* e, size_t n, const uint8_t* a, const uint8_t* b, bool dec, const uint8_t* q1,
+                const uint8_t* q2, size_t ntab, const uint32_t* idx, const uint8_t* scalars, uint8_t* v,
+                hbh_grouped_stats* stats) {
+  if (stats) *stats = hbh_grouped_stats{0, 0, 0, 0};
+  if (n == 0) return HBH_OK;
+  if (!a || !b || !q1 || (dec && !q2) || !v) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_idx(idx, n, ntab);
+  if (rc) return rc;
+  std::vector<uint32_t> iota;
+  if (!idx) {  // identity map: every item is alone in its group
+    iota.resize(n);
+    for (size_t i = 0; i < n; i++) iota[i] = (uint32_t)i;
+    idx = iota.data();
+  }
+  GroupPlan P;
+  if (!plan_groups(n, idx, ntab, 2, P)) return fail(HBH_ERR_ARG, "index out of range");
+  std::vector<uint8_t> r;
+  rc = rlc_scalars(n, scalars, r);
+  if (rc) return rc;
+  const size_t bsz = dec ? HBH_G1_BYTES : HBH_G2_BYTES;
+  const size_t nc = P.comb.size();
+  std::vector<uint8_t> gv(nc, 0);
+  std::vector<uint32_t> packed;
+  if (nc) {
+    if (ntab > (size_t)1 << 30) return fail(HBH_ERR_ARG, "batch too large");
+    EngineCall call(e, nullptr, true);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
+    GroupDev d;
+    rc = upload_plan(e, s, P, r, packed, d);
+    if (rc) return rc;
+    HBH_CHECK(upload(s, e->in_p1, a, n * HBH_G1_BYTES));
+    HBH_CHECK(upload(s, dec ? e->in_p2 : e->in_d, b, n * bsz));
+    HBH_CHECK(upload(s, e->in_q1, q1, ntab * HBH_G2_BYTES));
+    if (dec) HBH_CHECK(upload(s, e->in_q2, q2, ntab * HBH_G2_BYTES));
+    HBH_CHECK(e->work.ensure(2 * (size_t)d.ntile * hbl::group_tile_bytes(true)));
+    HBH_CHECK(e->out_x.ensure(nc * HBH_G1_BYTES));
+    HBH_CHECK(e->in_c.ensure(nc * bsz));
+    HBH_CHECK(e->out_v.ensure(nc));
+    {
+      StageScope tm(e, s, HBH_STAGE_CURVE);
+      rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p);
+      if (!rc) rc = launch_group_sums(e, s, !dec, n, dec ? e->in_p2.p : e->in_d.p, d, 1, e->in_c.p);
+      if (rc) return rc;
+    }
+    // sig: e(sum r pk, H) == e(g1, sum r sig);  dec: e(sum r D, H_uv) == e(sum r pk, W)
+    if (dec)
+      rc = run_pairing_dev(e, s, nc, e->out_x.p, e->in_q1.p, ntab, d.centry, e->in_c.p, e->in_q2.p, ntab, d.centry, 1,
+                           (uint8_t*)e->out_v.p);
+    else
+      rc = run_pairing_dev(e, s, nc, e->out_x.p, e->in_q1.p, ntab, d.centry, nullptr, e->in_c.p, nc, nullptr, 1,
+                           (uint8_t*)e->out_v.p);
+    if (rc) return rc;
+    HBH_CHECK(download(s, gv.data(), e->out_v, nc));
+    rc = call.finish();
+    if (rc) return rc;
+  }
+  // exact verdicts for the failed groups and the singles: the per-share call on the gathered items
+  std::vector<uint32_t> list;
+  plan_fallback(P, gv.data(), list);
+  if (stats) {
+    stats->groups = (uint32_t)nc;
+    for (uint8_t ok : gv) stats->groups_passed += ok ? 1 : 0;
+    stats->singles = (uint32_t)P.singles.size();
+    stats->fallback_items = (uint32_t)list.size();
+  }
+  std::memset(v, 1, n);
+  const size_t m = list.size();
+  if (!m) return HBH_OK;
+  std::vector<uint8_t> ga(m * HBH_G1_BYTES), gb(m * bsz), fv(m, 0);
+  std::vector<uint32_t> gi(m);
+  for (size_t k = 0; k < m; k++) {
+    std::memcpy(&ga[k * HBH_G1_BYTES], a + (size_t)list[k] * HBH_G1_BYTES, HBH_G1_BYTES);
+    std::memcpy(&gb[k * bsz], b + (size_t)list[k] * bsz, bsz);
+    gi[k] = idx[list[k]];
+  }
+  if (dec)
+    rc = run_pairing_eq_host(e, m, ga.data(), q1, ntab, gi.data(), gb.data(), q2, ntab, gi.data(), fv.data());
+  else
+    rc = run_pairing_eq_host(e, m, ga.data(), q1, ntab, gi.data(), nullptr, gb.data(), m, nullptr, fv.data());
+  if (rc) return rc;
+  for (size_t k = 0; k < m; k++) v[list[k]] = fv[k];
+  return HBH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hbh_verify_sig_shares_grouped(hbh_engine* e, size_t n, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* hashes, size_t ndocs, const uint32_t* doc_idx, const uint8_t* scalars,
+                                  uint8_t* v, hbh_grouped_stats* stats) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  return run_grouped(e, n, pks, sigs, false, hashes, nullptr, ndocs, doc_idx, scalars, v, stats);
+}
+
+int hbh_verify_dec_shares_grouped(hbh_engine* e, size_t n, const uint8_t* shares, const uint8_t* pks, const uint8_t* huv,
+                                  const uint8_t* w, size_t ncts, const uint32_t* ct_idx, const uint8_t* scalars,
+                                  uint8_t* v, hbh_grouped_stats* stats) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  return run_grouped(e, n, shares, pks, true, huv, w, ncts, ct_idx, scalars, v, stats);
+}
+
+int hbh_dbg_group_sums(hbh_engine* e, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts, size_t ngroups,
+                       const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1, uint8_t* out_g2) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if ((g1_pts && !out_g1) || (g2_pts && !out_g2)) return fail(HBH_ERR_ARG, "null pointer");
+  if (g1_pts) std::memset(out_g1, 0, ngroups * HBH_G1_BYTES);  // an absent entry sums to O
+  if (g2_pts) std::memset(out_g2, 0, ngroups * HBH_G2_BYTES);
+  if (n == 0) return HBH_OK;
+  if (!group_idx || !scalars) return fail(HBH_ERR_ARG, "null pointer");
+  GroupPlan P;
+  if (!plan_groups(n, group_idx, ngroups, 1, P)) return fail(HBH_ERR_ARG, "index out of range");
+  const std::vector<uint8_t> r(scalars, scalars + n * RLC_BYTES);
+  const size_t nc = P.comb.size();
+  std::vector<uint32_t> packed;
+  std::vector<uint8_t> s1(g1_pts ? nc * HBH_G1_BYTES : 0), s2(g2_pts ? nc * HBH_G2_BYTES : 0);
+  EngineCall call(e, nullptr, true);
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  GroupDev d;
+  int rc = upload_plan(e, s, P, r, packed, d);
+  if (rc) return rc;
+  HBH_CHECK(e->work.ensure(2 * (size_t)d.ntile * hbl::group_tile_bytes(true)));
+  StageScope tm(e, s, HBH_STAGE_CURVE);
+  if (g1_pts) {
+    HBH_CHECK(upload(s, e->in_p1, g1_pts, n * HBH_G1_BYTES));
+    HBH_CHECK(e->out_x.ensure(nc * HBH_G1_BYTES));
+    rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p);
+    if (rc) return rc;
+    HBH_CHECK(download(s, s1.data(), e->out_x, s1.size()));
+  }
+  if (g2_pts) {
+    HBH_CHECK(upload(s, e->in_d, g2_pts, n * HBH_G2_BYTES));
+    HBH_CHECK(e->in_c.ensure(nc * HBH_G2_BYTES));
+    rc = launch_group_sums(e, s, true, n, e->in_d.p, d, 1, e->in_c.p);
+    if (rc) return rc;
+    HBH_CHECK(download(s, s2.data(), e->in_c, s2.size()));
+  }
+  tm.stop();
+  rc = call.finish();
+  if (rc) return rc;
+  for (size_t c = 0; c < nc; c++) {
+    const size_t k = P.entry[P.comb[c]];
+    if (g1_pts) std::memcpy(out_g1 + k * HBH_G1_BYTES, &s1[c * HBH_G1_BYTES], HBH_G1_BYTES);
+    if (g2_pts) std::memcpy(out_g2 + k * HBH_G2_BYTES, &s2[c * HBH_G2_BYTES], HBH_G2_BYTES);
+  }
+  return HBH_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Host-side launchers of the HIP kernels.  Each kernel family lives in its own translation unit
-// (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip) so the Makefile
+// (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip, k_rlc.hip) so the Makefile
 // compiles them in parallel; engine.hip owns the C ABI, device buffers and streams and calls only
 // these functions.  Its host arithmetic and planning live in host_fr.hpp, wire_host.hpp and ack_plan.hpp.
 #pragma once
@@ -154,6 +154,21 @@ hipError_t index_plus_one(hipStream_t s, int n, int m, const uint32_t* idx, uint
 // Commitment::evaluate(x) for n (commitment, x) requests; commitments of t+1 G1 points.  out[r].
 hipError_t commit_eval(hipStream_t s, int n, int t, const void* commits, const uint32_t* commit_idx, const uint32_t* xs,
                        void* out);
+
+// --------------------------------------------------------------- grouped random-combination sums (k_rlc.hip)
+// sum_i r_i P_i per group for the opt-in grouped share checks (group_plan.hpp plans the tiles).
+// group_sum_g*: tile t sums the items perm[tile_off[t] .. + tile_len[t]) (tile_len <= GROUP_TILE; item
+// indices < n) of pts (ABI words) with scalars (4 LE words per item, < 2^128, in the call's order) into
+// Jacobian tile sum t of tile_sums (group_tile_bytes(g2) each); max_len >= every tile_len sizes the
+// workgroups (one per tile).  group_join_g*: out[c] = the sum of the tiles [ctile[c], ctile[c + 1]) as an
+// affine ABI point (all-zero for O).
+size_t group_tile_bytes(bool g2);
+hipError_t group_sum_g1(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
+                        const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
+hipError_t group_sum_g2(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
+                        const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
+hipError_t group_join_g1(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
+hipError_t group_join_g2(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 
 // --------------------------------------------------------------- hashing to G2 (k_hash.hip)
 // The curve half of threshold_crypto hash_g2 for n 32-byte seeds (sha3_256 of each message) in device

@@ -4,6 +4,7 @@ Inputs are in the ABI point format (affine, canonical little-endian; infinity = 
 ``wire`` helpers convert from the reference's uncompressed wire encoding (pairing 0.14
 ``into_uncompressed``: big-endian, G2 as x.c1 || x.c0 || y.c1 || y.c0, 0x40 flag = infinity).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -57,6 +58,10 @@ def _join(points, size):
     if len(b) % size:
         raise ValueError("point buffer length %d is not a multiple of %d" % (len(b), size))
     return b
+
+
+# hbh_grouped_stats of one grouped share check (Engine.verify_*_shares_grouped)
+GroupedStats = collections.namedtuple("GroupedStats", "groups groups_passed singles fallback_items")
 
 
 class Engine:
@@ -251,6 +256,79 @@ class Engine:
         check(self._l.hbh_verify_dec_shares(self._h, n, keep[0][1], keep[1][1], keep[2][1], keep[3][1],
                                             len(hb) // G2_BYTES, pci, ctypes.cast(out, ctypes.c_void_p)))
         return bytes(out)[:n]
+
+    # ------------------------------------------------------------ grouped share checks (opt-in)
+    @staticmethod
+    def _rlc_scalars(scalars, n):
+        """(owner, pointer) of n 16-byte LE scalars (ints or packed bytes), or (None, None): the engine
+        then draws them from the OS."""
+        if scalars is None:
+            return None, None
+        if isinstance(scalars, (bytes, bytearray)):
+            raw = bytes(scalars)
+        else:
+            raw = b"".join(int(r).to_bytes(16, "little") for r in scalars)
+        if len(raw) != 16 * n:
+            raise ValueError("expected %d 16-byte scalars" % n)
+        return buf(raw or b"\0")
+
+    def verify_sig_shares_grouped(self, pks, sigs, hashes, doc_idx, scalars=None):
+        """verify_sig_shares with one pairing check per document on a random linear combination of
+        its shares, and the per-share check for the documents whose check fails
+        (hbh_verify_sig_shares_grouped): (verdicts, GroupedStats).  ``scalars`` None: the engine draws
+        them; given scalars (ints in [1, 2^128)) are used as they are -- the caller's responsibility."""
+        pkb, sgb, hb = _join(pks, G1_BYTES), _join(sigs, G2_BYTES), _join(hashes, G2_BYTES)
+        n = len(pkb) // G1_BYTES
+        if len(sgb) // G2_BYTES != n:
+            raise ValueError("pks/sigs length mismatch")
+        di, pdi = _u32(doc_idx, n)
+        rk, pr = self._rlc_scalars(scalars, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        st = _lib.GroupedStats()
+        keep = [buf(x) for x in (pkb, sgb, hb)]
+        check(self._l.hbh_verify_sig_shares_grouped(self._h, n, keep[0][1], keep[1][1], keep[2][1],
+                                                    len(hb) // G2_BYTES, pdi, pr, ctypes.cast(out, ctypes.c_void_p),
+                                                    ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)))
+        return bytes(out)[:n], GroupedStats(st.groups, st.groups_passed, st.singles, st.fallback_items)
+
+    def verify_dec_shares_grouped(self, shares, pks, huv, w, ct_idx, scalars=None):
+        """verify_dec_shares with one pairing check per ciphertext (hbh_verify_dec_shares_grouped):
+        (verdicts, GroupedStats); scalars as verify_sig_shares_grouped."""
+        sb, pkb = _join(shares, G1_BYTES), _join(pks, G1_BYTES)
+        hb, wb = _join(huv, G2_BYTES), _join(w, G2_BYTES)
+        n = len(sb) // G1_BYTES
+        if len(pkb) // G1_BYTES != n or len(hb) != len(wb):
+            raise ValueError("shares/pks or huv/w length mismatch")
+        ci, pci = _u32(ct_idx, n)
+        rk, pr = self._rlc_scalars(scalars, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        st = _lib.GroupedStats()
+        keep = [buf(x) for x in (sb, pkb, hb, wb)]
+        check(self._l.hbh_verify_dec_shares_grouped(self._h, n, keep[0][1], keep[1][1], keep[2][1], keep[3][1],
+                                                    len(hb) // G2_BYTES, pci, pr, ctypes.cast(out, ctypes.c_void_p),
+                                                    ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)))
+        return bytes(out)[:n], GroupedStats(st.groups, st.groups_passed, st.singles, st.fallback_items)
+
+    def dbg_group_sums(self, g1_pts, g2_pts, ngroups, group_idx, scalars):
+        """The sums behind the grouped checks (hbh_dbg_group_sums): ([sum of r_i g1_pts[i] over the
+        items of group k], [the same for g2_pts]) for k < ngroups; a point list may be None (its
+        result is then None).  Tests only."""
+        b1 = None if g1_pts is None else _join(g1_pts, G1_BYTES)
+        b2 = None if g2_pts is None else _join(g2_pts, G2_BYTES)
+        n = len(group_idx)
+        if (b1 is not None and len(b1) != n * G1_BYTES) or (b2 is not None and len(b2) != n * G2_BYTES):
+            raise ValueError("points / group_idx length mismatch")
+        gi, pgi = _u32(group_idx, n)
+        rk, pr = self._rlc_scalars(scalars, n)
+        k1, k2 = buf(b1 or None), buf(b2 or None)
+        o1 = (ctypes.c_uint8 * max(ngroups * G1_BYTES, 1))()
+        o2 = (ctypes.c_uint8 * max(ngroups * G2_BYTES, 1))()
+        vp = ctypes.c_void_p
+        check(self._l.hbh_dbg_group_sums(self._h, n, k1[1], k2[1], ngroups, pgi, pr, ctypes.cast(o1, vp),
+                                         ctypes.cast(o2, vp)))
+        r1, r2 = bytes(o1), bytes(o2)
+        return (None if b1 is None else [r1[k * G1_BYTES:(k + 1) * G1_BYTES] for k in range(ngroups)],
+                None if b2 is None else [r2[k * G2_BYTES:(k + 1) * G2_BYTES] for k in range(ngroups)])
 
     def verify_ciphertexts(self, u, w, huv):
         """Ciphertext::verify batch (src/threshold_decrypt.rs:142)."""

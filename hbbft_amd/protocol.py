@@ -139,10 +139,21 @@ class BatchVerifier:
     opened since the last drain are added in one call when the next drain starts, the drain's share
     checks name slots (verify_*_set), and the slots are freed when the last instance of a key is
     released.  Keys that found no free slot take the stateless call, in the same drain.  Verdicts,
-    cache contents and counters are those of ``g2_capacity`` = 0 (the default: no set)."""
+    cache contents and counters are those of ``g2_capacity`` = 0 (the default: no set).
 
-    def __init__(self, engine, combine_engine=None, g2_capacity=0):
+    ``grouped`` = True sends a drain's signature-share and decryption-share checks through the grouped
+    calls (Engine.verify_*_shares_grouped, scalars drawn by the engine): one pairing check per document
+    or ciphertext on a random linear combination of its shares, the per-share check for the groups
+    that fail.  A reported invalid share is exact; a valid verdict is the reference's except with
+    probability at most 1 / (2^128 - 1) per group, and combine_and_verify_sig still checks the combined
+    signature.  Ciphertext checks, the cache and the counters are unchanged.  The grouped calls are
+    stateless, so ``grouped`` with ``g2_capacity`` > 0 is a ValueError.  Default: off."""
+
+    def __init__(self, engine, combine_engine=None, g2_capacity=0, grouped=False):
+        if grouped and g2_capacity > 0:
+            raise ValueError("grouped share checks are stateless: grouped=True takes no g2_capacity")
         self.eng = engine
+        self.grouped = bool(grouped)
         self._g2 = engine.g2_set(g2_capacity) if g2_capacity > 0 else None
         self._g2_slot = {}     # point -> slot
         self._g2_ref = {}      # point -> open keys that use it
@@ -492,6 +503,9 @@ class BatchVerifier:
         """The engine calls of a snapshot (any thread): [(kind, keys, verdict bytes)]."""
         fn = {"ct": "verify_ciphertexts", "sig": "verify_sig_shares", "dec": "verify_dec_shares"}
         nargs = {"ct": 3, "sig": 4, "dec": 5}
+        if self.grouped:  # no set (the constructor's rule), so every job carries the stateless arguments
+            return [(kind, keys, getattr(self.eng, fn[kind])(*args) if kind == "ct" else
+                     getattr(self.eng, fn[kind] + "_grouped")(*args)[0]) for kind, keys, args in jobs]
         return [(kind, keys, getattr(self.eng, fn[kind])(*args) if len(args) == nargs[kind] else self._run_set(kind, *args))
                 for kind, keys, args in jobs]
 

@@ -198,6 +198,40 @@ int hbh_verify_pairing_eq_set_dev(hbh_engine* eng, void* stream, size_t n,
                                   const void* d_p2, hbh_g2_set* set2, const void* d_q2_table, size_t nq2, const uint32_t* d_q2_idx,
                                   uint8_t* d_verdicts);
 
+/* ---------------------------------------------------------------- grouped share checks (opt-in)
+ * hbh_verify_sig_shares / hbh_verify_dec_shares with ONE pairing check per group of items that share a
+ * table entry (the shares of one document share H; the shares of one ciphertext share H_uv and W):
+ *   sig shares of document d:   e(sum r_i pk_i, H_d)    == e(g1, sum r_i sig_i)
+ *   dec shares of ciphertext c: e(sum r_i D_i,  H_uv_c) == e(sum r_i pk_i, W_c)
+ * with one scalar r_i in [1, 2^128) per item.  A group whose check holds reports every member valid; the
+ * items of a group whose check fails, and the items alone in their group, are re-checked share by share
+ * by the call above, so a verdict of 0 is always exact.  A verdict of 1 from a passed group is the
+ * reference's verdict except with probability at most 1 / (2^128 - 1) per group holding an invalid
+ * share -- PROVIDED the points are in the prime-order subgroups (the ABI's contract) and the scalars
+ * are uniform in [1, 2^128), independent of the inputs, and unknown to whoever chose the shares.
+ *   scalars == NULL: the engine draws n x 128 bits from the OS (getrandom) and replaces a zero draw.
+ *     This is the form the bound above is stated for.
+ *   scalars != NULL: n x 16 bytes, little-endian, USED AS GIVEN (an all-zero scalar is HBH_ERR_ARG).
+ *     The bound then holds only if the caller's scalars meet the conditions above: scalars a share
+ *     sender can predict let two invalid shares cancel inside a group.  For tests and for callers
+ *     with their own randomness.
+ * Index and argument errors, and n = 0, are as in the per-share calls.  stats (may be NULL): groups =
+ * groups of at least two items (each one pairing check), groups_passed = those whose check held,
+ * singles = items alone in their group, fallback_items = items re-checked share by share (the items of
+ * the failed groups plus the singles).  The group sums are accounted under HBH_STAGE_CURVE, the group
+ * checks and the fallback under HBH_STAGE_PAIRING / HBH_STAGE_PREPARE as any pairing check.  Stateless:
+ * no _dev, pool or G2-set form.  What the grouped call costs against the per-share call on an MI355X:
+ * profiles/r16/README.md. */
+typedef struct {
+  uint32_t groups, groups_passed, singles, fallback_items;
+} hbh_grouped_stats;
+int hbh_verify_sig_shares_grouped(hbh_engine* eng, size_t n, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* hashes, size_t ndocs, const uint32_t* doc_idx,
+                                  const uint8_t* scalars, uint8_t* verdicts, hbh_grouped_stats* stats);
+int hbh_verify_dec_shares_grouped(hbh_engine* eng, size_t n, const uint8_t* shares, const uint8_t* pks,
+                                  const uint8_t* huv, const uint8_t* w, size_t ncts, const uint32_t* ct_idx,
+                                  const uint8_t* scalars, uint8_t* verdicts, hbh_grouped_stats* stats);
+
 /* ---------------------------------------------------------------- combine (interpolate at 0)
  * threshold_crypto interpolate(t, samples) for `ncomb` independent combines of exactly t+1
  * samples each (the first t+1 of the reference's iterator, in its order): out[c] =
@@ -550,6 +584,13 @@ int hbh_dbg_pairing(hbh_engine* eng, size_t n, const uint8_t* p, const uint8_t* 
  * HBH_HASH_ROUNDS).  A low value leaves messages unresolved on purpose, for the tests of the host-stage
  * path of the leftovers and of hbh_hash_g2_dev's report. */
 int hbh_dbg_set_hash_rounds(hbh_engine* eng, int rounds);
+/* hbh_dbg_group_sums: the sums the grouped share checks feed their pairing checks, for parity tests:
+ * out_g1[k] = sum of r_i g1_pts[i] and out_g2[k] = sum of r_i g2_pts[i] over the items with
+ * group_idx[i] == k, k < ngroups (ABI points, all-zero when the sum is the point at infinity or no item
+ * names k; groups of one item are summed too).  g1_pts / g2_pts may be NULL (that output is then not
+ * written); scalars: n x 16 bytes little-endian, any value.  A group index >= ngroups is HBH_ERR_ARG. */
+int hbh_dbg_group_sums(hbh_engine* eng, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts, size_t ngroups,
+                       const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1, uint8_t* out_g2);
 
 #ifdef __cplusplus
 }
