@@ -32,6 +32,7 @@ SIGNATURES = [
     ("hbh_verify_sig_shares_grouped", _I, [_P, _SZ, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_verify_dec_shares_grouped", _I, [_P, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_dbg_group_sums", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
+    ("hbh_engine_set_group_sum_impl", _I, [_P, _I]),
     ("hbh_verify_pairing_eq_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_dbg_pairing", _I, [_P, _SZ, _P, _P, _P]),
     ("hbh_interpolate_g2", _I, [_P, _SZ, _I, _P, _P, _P, _P]),
@@ -122,6 +123,8 @@ AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPL
 HASH_AUTO, HASH_HOST, HASH_DEVICE = 0, 1, 2  # HBH_HASH_*
 HASH_ROUNDS = 32  # HBH_HASH_ROUNDS
 AUTO_HASH_DEVICE_MIN = 4096  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r14)
+GSUM_AUTO, GSUM_CHAIN, GSUM_BUCKET = 0, 1, 2  # HBH_GSUM_*
+AUTO_GSUM_G1_BUCKET_MIN, AUTO_GSUM_G2_BUCKET_MIN = 0, 0  # HBH_AUTO_GSUM_G*_BUCKET_MIN (0: never; profiles/r17)
 GROUP_TILE = 128  # csrc/group_plan.hpp GROUP_TILE: items per tile of the grouped share checks' sums
 
 

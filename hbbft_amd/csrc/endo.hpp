@@ -5,13 +5,13 @@
 
 namespace hb {
 
-__device__ __forceinline__ void load_g1(const uint32_t* w, Fp& x, Fp& y, bool& inf) {
+HB_HD void load_g1(const uint32_t* w, Fp& x, Fp& y, bool& inf) {
   G1Aff a = g1_from_words(w);
   x = a.x;
   y = a.y;
   inf = a.inf;
 }
-__device__ __forceinline__ void load_g2(const uint32_t* w, Fp2& x, Fp2& y, bool& inf) {
+HB_HD void load_g2(const uint32_t* w, Fp2& x, Fp2& y, bool& inf) {
   G2Aff a = g2_from_words(w);
   x = a.x;
   y = a.y;

@@ -119,6 +119,7 @@ struct hbh_engine {
   int impl = HBH_IMPL_AUTO;  // pairing implementation (hbh_engine_set_pairing_impl)
   int ack_impl = HBH_ACK_AUTO;  // Ack-check kernel of commitment sets (hbh_engine_set_ack_impl)
   int dec_impl = HBH_DEC_AUTO;  // point-decoding kernels (hbh_engine_set_decode_impl)
+  int gsum_impl = HBH_GSUM_AUTO;  // group sums of the grouped share checks (hbh_engine_set_group_sum_impl)
   int hash_impl = HBH_HASH_AUTO;  // where the curve half of hash_g2 runs (hbh_engine_set_hash_impl)
   int hash_rounds = HBH_HASH_ROUNDS;  // sampler rounds of the device form (hbh_dbg_set_hash_rounds)
   StageTimer timer;
@@ -692,6 +693,15 @@ int hbh_engine_set_decode_impl(hbh_engine* e, int impl) {
     return fail(HBH_ERR_ARG, "unknown point-decoding implementation");
   std::lock_guard<std::mutex> lk(e->mu);
   e->dec_impl = impl;
+  return HBH_OK;
+}
+
+int hbh_engine_set_group_sum_impl(hbh_engine* e, int impl) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (impl != HBH_GSUM_AUTO && impl != HBH_GSUM_CHAIN && impl != HBH_GSUM_BUCKET)
+    return fail(HBH_ERR_ARG, "unknown group-sum implementation");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->gsum_impl = impl;
   return HBH_OK;
 }
 
@@ -2194,8 +2204,16 @@ int upload_plan(hbh_engine* e, hipStream_t s, const GroupPlan& P, const std::vec
 int launch_group_sums(hbh_engine* e, hipStream_t s, bool g2, size_t n, const void* d_pts, const GroupDev& d, int region,
                       void* d_out) {
   void* tiles = (uint8_t*)e->work.p + (size_t)region * d.ntile * hbl::group_tile_bytes(true);
-  HBH_CHECK((g2 ? hbl::group_sum_g2 : hbl::group_sum_g1)(s, d.ntile, (int)n, d.max_len, d_pts, d.scalars, d.perm,
-                                                        d.tile_off, d.tile_len, tiles));
+  // the form of this sum: forced, or AUTO by the items of the call (a threshold of 0: never BUCKET)
+  const size_t bucket_min = g2 ? HBH_AUTO_GSUM_G2_BUCKET_MIN : HBH_AUTO_GSUM_G1_BUCKET_MIN;
+  const bool bucket =
+      e->gsum_impl == HBH_GSUM_BUCKET || (e->gsum_impl == HBH_GSUM_AUTO && bucket_min > 0 && n >= bucket_min);
+  if (bucket)
+    HBH_CHECK((g2 ? hbl::group_bucket_g2 : hbl::group_bucket_g1)(s, d.ntile, (int)n, d.max_len, d_pts, d.scalars, d.perm,
+                                                                 d.tile_off, d.tile_len, tiles));
+  else
+    HBH_CHECK((g2 ? hbl::group_sum_g2 : hbl::group_sum_g1)(s, d.ntile, (int)n, d.max_len, d_pts, d.scalars, d.perm,
+                                                          d.tile_off, d.tile_len, tiles));
   HBH_CHECK((g2 ? hbl::group_join_g2 : hbl::group_join_g1)(s, d.ncomb, d.ctile, tiles, d_out));
   return HBH_OK;
 }

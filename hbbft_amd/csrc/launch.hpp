@@ -167,6 +167,12 @@ hipError_t group_sum_g1(hipStream_t s, int ntile, int n, int max_len, const void
                         const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
 hipError_t group_sum_g2(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
                         const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
+// group_bucket_g*: the tile sums of group_sum_g* by the windowed bucket method (k_rlc_bucket.hip): same
+// arguments, same tile records, so group_join_g* serves both.
+hipError_t group_bucket_g1(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
+                           const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
+hipError_t group_bucket_g2(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
+                           const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
 hipError_t group_join_g1(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 hipError_t group_join_g2(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 

@@ -628,6 +628,13 @@ class Engine:
         forms; both forms write the same bytes."""
         check(self._l.hbh_engine_set_decode_impl(self._h, int(impl)))
 
+    def set_group_sum_impl(self, impl):
+        """HBH_GSUM_*: 0 = auto (default: the bucket form from AUTO_GSUM_G1_BUCKET_MIN /
+        AUTO_GSUM_G2_BUCKET_MIN items per call, 0 = never), 1 = one double-and-add chain per item,
+        2 = windowed buckets per tile.  Governs the group sums of the grouped share checks and
+        dbg_group_sums; both forms give the same bytes and verdicts."""
+        check(self._l.hbh_engine_set_group_sum_impl(self._h, int(impl)))
+
     # ------------------------------------------------------------ profiling
     def set_profiling(self, on):
         check(self._l.hbh_engine_set_profiling(self._h, 1 if on else 0))

@@ -194,3 +194,66 @@ def wire_decode_critical_path(group, form):
 def wire_split_model_ratio(group):
     """Predicted SPLIT / LANE time of a small batch (op model only: no issue rate, no memory)."""
     return wire_decode_critical_path(group, "split") / wire_decode_critical_path(group, "lane")
+
+
+# ---------------------------------------------------------------------------- group sums (grouped share checks)
+# One tile of L items of the sums sum_i r_i P_i (r_i: 128 unstructured random bits), per form
+# (hbh_engine_set_group_sum_impl), in Fp products from the per-operation weights above.
+G2_ADD = (11 * F2M + 5 * F2S, 0)         # add-2007-bl over Fp2
+GSUM_OPS = {"g1": (G1_DBL[0], G1_MADD[0], G1_ADD[0]), "g2": (G2_DBL[0], G2_MADD[0], G2_ADD[0])}
+GSUM_WINDOWS = {"g1": 64, "g2": 32}      # two-bit windows: 128 bits of r (G1), d0 and d1 < |x| < 2^64 (G2)
+GSUM_TAIL_SEGS = 8                       # csrc/group_bucket.hpp TAIL_SEGS
+GSUM_D2_RATE = 1.0 - (X_ABS * X_ABS) / 2.0 ** 128   # share of the scalars >= |x|^2: the psi^2(P) term
+
+
+def _gsum_tail(kind):
+    """(doublings, additions) of the bucket form's tail and the same for its longest lane: TAIL_SEGS
+    Horner runs of windows / TAIL_SEGS windows, each shifted by its weight, then a tree."""
+    seg = GSUM_WINDOWS[kind] // GSUM_TAIL_SEGS
+    dbl = sum(2 * (seg - 1) + 2 * seg * s for s in range(GSUM_TAIL_SEGS))
+    add = GSUM_TAIL_SEGS * (seg - 1) + GSUM_TAIL_SEGS - 1
+    path = (2 * (seg - 1) + 2 * seg * (GSUM_TAIL_SEGS - 1), (seg - 1) + GSUM_TAIL_SEGS.bit_length() - 1)
+    return (dbl, add), path
+
+
+def group_sum_ops(kind, impl, L):
+    """Fp products issued for one tile of L items ("g1" / "g2", "chain" / "bucket"), expected over
+    random scalars.
+      chain (k_group_sum): one double-and-add chain per (item, digit): G1 128 doublings and 64 mixed
+        additions per item; G2 two chains of 64 and 32, the psi^2(P) addition for r >= |x|^2 and the
+        addition of the second chain into the first; then L - 1 additions of the tree.
+      bucket (k_group_bucket): 3/4 of the (term, window) digits are nonzero, one mixed addition each
+        (G1: L terms x 64 windows; G2: 2 L terms x 32 windows, plus the psi^2(P) terms in window 0);
+        3 additions and a doubling per window to reduce the buckets; the tail."""
+    dbl, madd, add = GSUM_OPS[kind]
+    if impl == "chain":
+        if kind == "g1":
+            return L * (128 * dbl + 64 * madd) + (L - 1) * add
+        return 2 * L * (64 * dbl + 32 * madd) + L * GSUM_D2_RATE * madd + L * add + (L - 1) * add
+    if impl != "bucket":
+        raise ValueError(impl)
+    nw = GSUM_WINDOWS[kind]
+    terms = L if kind == "g1" else 2 * L
+    acc = 0.75 * terms * nw * madd + (L * GSUM_D2_RATE * madd if kind == "g2" else 0)
+    (tdbl, tadd), _ = _gsum_tail(kind)
+    return acc + nw * (3 * add + dbl) + tdbl * dbl + tadd * add
+
+
+def group_sum_critical_path(kind, impl, L):
+    """Fp-product times of the longest lane of one tile's workgroup.  Under SIMT a lane executes a
+    masked addition whenever any lane of its wave takes it, so a chain pays the addition at every bit
+    and a bucket lane at every term."""
+    dbl, madd, add = GSUM_OPS[kind]
+    if impl == "chain":
+        width = 64
+        while width < L:
+            width *= 2
+        tree = (width.bit_length() - 1) * add
+        if kind == "g1":
+            return 128 * (dbl + madd) + tree
+        return 64 * (dbl + madd) + madd + add + tree
+    if impl != "bucket":
+        raise ValueError(impl)
+    _, (pdbl, padd) = _gsum_tail(kind)
+    slots = L if kind == "g1" else 2 * L + L * GSUM_D2_RATE   # window 0's wave takes the psi^2(P) terms
+    return slots * madd + (3 * add + dbl) + pdbl * dbl + padd * add

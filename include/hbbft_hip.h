@@ -231,6 +231,25 @@ int hbh_verify_sig_shares_grouped(hbh_engine* eng, size_t n, const uint8_t* pks,
 int hbh_verify_dec_shares_grouped(hbh_engine* eng, size_t n, const uint8_t* shares, const uint8_t* pks,
                                   const uint8_t* huv, const uint8_t* w, size_t ncts, const uint32_t* ct_idx,
                                   const uint8_t* scalars, uint8_t* verdicts, hbh_grouped_stats* stats);
+/* Kernels of the two group sums of a grouped call and of hbh_dbg_group_sums (same bytes from either: the
+ * scalars are the same integers, only the order of the additions differs, and the sums leave the device
+ * as canonical affine points; verdicts, hbh_grouped_stats and the bound above do not depend on the form):
+ *   HBH_GSUM_CHAIN (k_rlc.hip): one double-and-add chain per (item, digit of the scalar); every item
+ *     pays its own doublings.
+ *   HBH_GSUM_BUCKET (k_rlc_bucket.hip): two-bit windows, three buckets per window in LDS, one wave per
+ *     tile of a group; the doublings are paid once per tile.
+ *   HBH_GSUM_AUTO (the default): BUCKET for a sum of a call of at least HBH_AUTO_GSUM_G1_BUCKET_MIN (a
+ *     G1 sum) / HBH_AUTO_GSUM_G2_BUCKET_MIN (the G2 sum) items (0: never), CHAIN below; the two sums of
+ *     one call may take different forms.  Thresholds: the smallest swept size from which BUCKET's median
+ *     HBH_STAGE_CURVE time is below CHAIN's by more than both cells' min-max spread, at that and every
+ *     larger swept size (profiles/r17/README.md, tools/grouped_bench.py --sum-impl both).
+ * A forced form runs for every call.  Any other value returns HBH_ERR_ARG and changes nothing. */
+#define HBH_GSUM_AUTO 0
+#define HBH_GSUM_CHAIN 1
+#define HBH_GSUM_BUCKET 2
+#define HBH_AUTO_GSUM_G1_BUCKET_MIN 0
+#define HBH_AUTO_GSUM_G2_BUCKET_MIN 0
+int hbh_engine_set_group_sum_impl(hbh_engine* eng, int impl);
 
 /* ---------------------------------------------------------------- combine (interpolate at 0)
  * threshold_crypto interpolate(t, samples) for `ncomb` independent combines of exactly t+1

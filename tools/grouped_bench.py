@@ -9,7 +9,17 @@ compared before anything is timed.
 
     python tools/grouped_bench.py --reps 7 --out profiles/r16
 
-writes grouped_bench.json (every sample) and grouped_bench.md (min / median / max per cell)."""
+writes grouped_bench.json (every sample) and grouped_bench.md (min / median / max per cell).
+
+--sum-impl chain|bucket forces that form of the group sums (hbh_engine_set_group_sum_impl) for the grouped
+call; --sum-impl both runs the grouped call under each form in turn in this process, cell by cell (one
+more column per form), and adds a sweep of the sums alone: hbh_dbg_group_sums on the G1 points and on the
+G2 points of each signature shape, one side per call, under each form alternately with profiling on --
+the HBH_STAGE_CURVE time per kind of sum and form that the AUTO thresholds are decided from (the rule of
+include/hbbft_hip.h: the smallest swept size from which BUCKET's median is below CHAIN's by more than both
+cells' min-max spread, at that and every larger swept size).  The JSON is then {"cells", "sums", "auto"}.
+
+    python tools/grouped_bench.py --sum-impl both --reps 7 --out profiles/r17"""
 import argparse
 import json
 import os
@@ -23,7 +33,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import bls12_381 as C  # noqa: E402
-from hbbft_amd._lib import STAGE_CURVE, STAGE_PAIRING, STAGE_PREPARE  # noqa: E402
+from hbbft_amd._lib import GSUM_AUTO, GSUM_BUCKET, GSUM_CHAIN, STAGE_CURVE, STAGE_PAIRING, STAGE_PREPARE  # noqa: E402
 from hbbft_amd.engine import Engine, g1_abi_from_uncompressed as g1a, g2_abi_from_uncompressed as g2a  # noqa: E402
 
 R = C.R
@@ -34,7 +44,10 @@ SHAPES = [  # (kind, shares, groups)
     ("sign", 10000, 100),    # an epoch's coins: 100 documents of 100 shares
     ("sign", 512, 8),
     ("decrypt", 65536, 1024),
+    ("decrypt", 10000, 100),
 ]
+FORMS = {None: [("grouped", GSUM_AUTO)], "chain": [("grouped", GSUM_CHAIN)], "bucket": [("grouped", GSUM_BUCKET)],
+         "both": [("grouped_chain", GSUM_CHAIN), ("grouped_bucket", GSUM_BUCKET)]}
 MIXES = [("all valid", 0.0), ("1 % of groups bad", 0.01), ("10 % of groups bad", 0.10)]
 
 
@@ -88,55 +101,141 @@ def stages(eng, fn):
     return t[0], t[1] + t[2]
 
 
-def measure(eng, kind, n, ngroups, mix, frac, reps, rng):
+def measure(eng, kind, n, ngroups, mix, frac, reps, rng, forms):
     nbad = 0 if frac == 0 else max(1, round(frac * ngroups))
     bad = sorted(rng.sample(range(ngroups), nbad))
     inp = inputs(eng, rng, kind, n, ngroups, bad)
     plain = (eng.verify_sig_shares if kind == "sign" else eng.verify_dec_shares)
-    grouped = (eng.verify_sig_shares_grouped if kind == "sign" else eng.verify_dec_shares_grouped)
+    grouped_call = (eng.verify_sig_shares_grouped if kind == "sign" else eng.verify_dec_shares_grouped)
     args = inp["args"]
-    got, stats = grouped(*args)  # first calls: verdicts, and the warm-up of both paths
-    assert plain(*args) == inp["want"] == got, "verdicts differ"
-    assert stats.groups == ngroups and stats.groups_passed == ngroups - nbad and stats.fallback_items == nbad * (n // ngroups)
+
+    def grouped(impl):
+        eng.set_group_sum_impl(impl)
+        try:
+            return grouped_call(*args)
+        finally:
+            eng.set_group_sum_impl(GSUM_AUTO)
+
+    want = plain(*args)  # first calls: verdicts, and the warm-up of every path
+    assert want == inp["want"], "verdicts differ"
+    for _, impl in forms:
+        got, stats = grouped(impl)
+        assert got == want, "verdicts differ"
+        assert (stats.groups == ngroups and stats.groups_passed == ngroups - nbad
+                and stats.fallback_items == nbad * (n // ngroups))
     for _ in range(2):
         plain(*args)
-        grouped(*args)
-    wall = {"per_share": [], "grouped": []}
+        for _, impl in forms:
+            grouped(impl)
+    wall = {name: [] for name in ["per_share"] + [f for f, _ in forms]}
     for _ in range(reps):
-        for name, fn in (("per_share", plain), ("grouped", grouped)):
+        for name, fn in [("per_share", lambda: plain(*args))] + [(f, lambda i=i: grouped(i)) for f, i in forms]:
             t0 = time.perf_counter()
-            fn(*args)
+            fn()
             wall[name].append((time.perf_counter() - t0) * 1e3)
     bad_set = set(bad)
     fallback = [i for i in range(n) if inp["grp"][i] in bad_set]
     fargs = subset(kind, inp, fallback) if fallback else None
-    split = {"curve": [], "pairing_all": [], "pairing_fallback": [], "per_share_pairing": []}
+    split = {"pairing_fallback": [], "per_share_pairing": []}
+    for f, _ in forms:
+        split["curve" + f[len("grouped"):]] = []
+        split["pairing_all" + f[len("grouped"):]] = []
     for _ in range(reps):
-        c, p = stages(eng, lambda: grouped(*args))
-        split["curve"].append(c)
-        split["pairing_all"].append(p)
+        for f, impl in forms:
+            c, p = stages(eng, lambda: grouped(impl))
+            split["curve" + f[len("grouped"):]].append(c)
+            split["pairing_all" + f[len("grouped"):]].append(p)
         split["pairing_fallback"].append(stages(eng, lambda: plain(*fargs))[1] if fargs else 0.0)
         split["per_share_pairing"].append(stages(eng, lambda: plain(*args))[1])
     row = dict(kind=kind, shares=n, groups=ngroups, mix=mix, bad_groups=nbad, fallback_items=stats.fallback_items,
                wall_ms={k: cell(v) for k, v in wall.items()}, device_ms={k: cell(v) for k, v in split.items()})
-    row["ratio_median"] = row["wall_ms"]["per_share"]["median"] / row["wall_ms"]["grouped"]["median"]
-    return row
+    for f, _ in forms:
+        row["ratio_median" + f[len("grouped"):]] = row["wall_ms"]["per_share"]["median"] / row["wall_ms"][f]["median"]
+    return row, inp
+
+
+def sums_alone(eng, inp, n, ngroups, reps, rng):
+    """HBH_STAGE_CURVE ms of hbh_dbg_group_sums on one side (the G1 points, then the G2 points of a
+    signature shape) under each form: bytes compared first, two warm-ups each, then reps alternations."""
+    pks, sigs, _, grp = inp["args"]
+    scalars = bytes(rng.getrandbits(8) for _ in range(16 * n))
+    out = []
+    for kind, pts in (("g1", (pks, None)), ("g2", (None, sigs))):
+        def run(impl):
+            eng.set_group_sum_impl(impl)
+            try:
+                return eng.dbg_group_sums(pts[0], pts[1], ngroups, grp, scalars)
+            finally:
+                eng.set_group_sum_impl(GSUM_AUTO)
+        assert run(GSUM_CHAIN) == run(GSUM_BUCKET), "sums differ"
+        for _ in range(2):
+            run(GSUM_CHAIN)
+            run(GSUM_BUCKET)
+        t = {"chain": [], "bucket": []}
+        for _ in range(reps):
+            for name, impl in (("chain", GSUM_CHAIN), ("bucket", GSUM_BUCKET)):
+                t[name].append(stages(eng, lambda: run(impl))[0])
+        out.append(dict(kind=kind, items=n, groups=ngroups, curve_ms={k: cell(v) for k, v in t.items()}))
+    return out
+
+
+def auto_thresholds(sums):
+    """Per kind of sum: the smallest swept size from which BUCKET's median CURVE time is below CHAIN's by
+    more than both cells' min-max spread, at that and every larger swept size; 0 when no size qualifies."""
+    auto = {}
+    for kind in ("g1", "g2"):
+        rows = sorted((r for r in sums if r["kind"] == kind), key=lambda r: r["items"])
+        thr = 0
+        for r in reversed(rows):
+            c, b = r["curve_ms"]["chain"], r["curve_ms"]["bucket"]
+            gain = c["median"] - b["median"]
+            r["bucket_wins"] = bool(gain > c["max"] - c["min"] and gain > b["max"] - b["min"])
+            if not r["bucket_wins"]:
+                break
+            thr = r["items"]
+        for r in rows:  # the sizes below the break are judged too, for the record
+            if "bucket_wins" not in r:
+                c, b = r["curve_ms"]["chain"], r["curve_ms"]["bucket"]
+                gain = c["median"] - b["median"]
+                r["bucket_wins"] = bool(gain > c["max"] - c["min"] and gain > b["max"] - b["min"])
+        auto[kind] = thr
+    return auto
 
 
 def fmt(c):
     return "%.2f / %.2f / %.2f" % (c["min"], c["median"], c["max"])
 
 
-def table(rows):
-    out = ["| shape | mix | fallback items | per-share wall ms | grouped wall ms | per-share / grouped (medians) | "
-           "grouped: CURVE ms | grouped: PREPARE + PAIRING ms | of which fallback ms | per-share: PREPARE + PAIRING ms |",
-           "|---|---|---|---|---|---|---|---|---|---|"]
+def table(rows, forms):
+    tails = [f[len("grouped"):] for f, _ in forms]
+    head = ["shape", "mix", "fallback items", "per-share wall ms"]
+    head += ["%s wall ms" % f.replace("_", ", ") for f, _ in forms]
+    head += ["per-share / %s (medians)" % f.replace("_", ", ") for f, _ in forms]
+    head += ["%s: CURVE ms" % f.replace("_", ", ") for f, _ in forms]
+    head += ["%s: PREPARE + PAIRING ms" % f.replace("_", ", ") for f, _ in forms]
+    head += ["of which fallback ms", "per-share: PREPARE + PAIRING ms"]
+    out = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
     for r in rows:
         w, d = r["wall_ms"], r["device_ms"]
-        out.append("| %s %d in %d | %s | %d | %s | %s | %.2f | %s | %s | %s | %s |" % (
-            r["kind"], r["shares"], r["groups"], r["mix"], r["fallback_items"], fmt(w["per_share"]), fmt(w["grouped"]),
-            r["ratio_median"], fmt(d["curve"]), fmt(d["pairing_all"]), fmt(d["pairing_fallback"]),
-            fmt(d["per_share_pairing"])))
+        col = ["%s %d in %d" % (r["kind"], r["shares"], r["groups"]), r["mix"], "%d" % r["fallback_items"],
+               fmt(w["per_share"])]
+        col += [fmt(w[f]) for f, _ in forms]
+        col += ["%.2f" % r["ratio_median" + t] for t in tails]
+        col += [fmt(d["curve" + t]) for t in tails]
+        col += [fmt(d["pairing_all" + t]) for t in tails]
+        col += [fmt(d["pairing_fallback"]), fmt(d["per_share_pairing"])]
+        out.append("| " + " | ".join(col) + " |")
+    return "\n".join(out) + "\n"
+
+
+def sums_table(sums, auto):
+    out = ["| sum | items in groups | CHAIN: CURVE ms | BUCKET: CURVE ms | BUCKET wins beyond both spreads |", "|---|---|---|---|---|"]
+    for r in sums:
+        out.append("| %s | %d in %d | %s | %s | %s |" % (r["kind"], r["items"], r["groups"], fmt(r["curve_ms"]["chain"]),
+                                                      fmt(r["curve_ms"]["bucket"]), "yes" if r["bucket_wins"] else "no"))
+    out.append("")
+    out.append("AUTO by the rule: HBH_AUTO_GSUM_G1_BUCKET_MIN %d, HBH_AUTO_GSUM_G2_BUCKET_MIN %d (0: never)"
+               % (auto["g1"], auto["g2"]))
     return "\n".join(out) + "\n"
 
 
@@ -145,25 +244,37 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="alternations per cell (>= 5)")
     ap.add_argument("--out", default=None, help="directory for grouped_bench.json and grouped_bench.md")
     ap.add_argument("--only", type=int, default=None, help="index of one shape (rehearsal)")
+    ap.add_argument("--sum-impl", choices=["chain", "bucket", "both"], default=None,
+                    help="form of the group sums (default: the engine's AUTO)")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
+    forms = FORMS[a.sum_impl]
     eng = Engine(0)
     rng = random.Random(16)
-    rows = []
+    rows, sums = [], []
     for k, (kind, n, ngroups) in enumerate(SHAPES):
         if a.only is not None and k != a.only:
             continue
         for mix, frac in MIXES:
-            rows.append(measure(eng, kind, n, ngroups, mix, frac, a.reps, rng))
-            print(json.dumps({k_: v for k_, v in rows[-1].items() if k_ not in ("wall_ms", "device_ms")}), flush=True)
+            row, inp = measure(eng, kind, n, ngroups, mix, frac, a.reps, rng, forms)
+            rows.append(row)
+            print(json.dumps({k_: v for k_, v in row.items() if k_ not in ("wall_ms", "device_ms")}), flush=True)
+            if a.sum_impl == "both" and kind == "sign" and frac == 0.0:
+                sums += sums_alone(eng, inp, n, ngroups, a.reps, rng)
+                print(json.dumps([{k_: v for k_, v in r.items() if k_ != "curve_ms"} for r in sums[-2:]]), flush=True)
     eng.close()
-    md = "min / median / max of %d alternated runs per cell\n\n" % a.reps + table(rows)
+    md = "min / median / max of %d alternated runs per cell\n\n" % a.reps + table(rows, forms)
+    doc = rows
+    if a.sum_impl == "both":
+        auto = auto_thresholds(sums)
+        md += "\nThe sums alone (hbh_dbg_group_sums, one side per call; device ms under HBH_STAGE_CURVE)\n\n" + sums_table(sums, auto)
+        doc = {"cells": rows, "sums": sums, "auto": auto}
     print(md)
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "grouped_bench.json"), "w") as f:
-            json.dump(rows, f, indent=1)
+            json.dump(doc, f, indent=1)
             f.write("\n")
         with open(os.path.join(a.out, "grouped_bench.md"), "w") as f:
             f.write(md)
