@@ -255,6 +255,8 @@ struct LaneOcto {
   static HP_D bool leader() { return (threadIdx.x & 7) == 0; }
   static HP_D bool value_writer() { return o_idx() == 0; }  // pair 0
   using Walk = HJac;
+  template <bool W1, bool W2, int GEN>
+  using Park = NoPark;  // T and P stay in registers
   static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_o(T); }
   static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_o(T, xQ, yQ); }
 
@@ -285,9 +287,9 @@ struct LaneOcto {
   static HP_D H12 frob2(const H12& f) { return h12_frob2_o(f); }
 
   // both sides' raw lines first, then their evaluation at P in one round of four Fp products
-  template <bool G1, bool G2, class RA, class RB, class ST>
+  template <bool G1, bool G2, bool WALK_FIRST, class RA, class RB, class ST>
   static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
-                              HLine& lb) {
+                              HLine& lb, const NoPark&) {
     const HLine ra = raw_a();
     const HLine rb = raw_b();
     Fp r[4];

@@ -11,6 +11,7 @@ namespace hbs {
 constexpr int PAIR_STEPS = 68;   // 63 doubling + 5 addition steps of |x|
 constexpr int PL_Q4 = 11;        // 16-byte chunks per (line, lane component): c0, c1, c4 = 42 words (+2 pad)
 constexpr int STASH_WORDS = 72;  // 6 packed Fp per lane
+static_assert(PARK_WORDS <= STASH_WORDS, "the Miller loop parks T and P in the stash (pfp.hpp PairPark)");
 
 // ---------------------------------------------------------------- LDS stash (6 components)
 // component reduced to [0, 2p) (< 2^382) and packed 14 x 28 -> 12 x 32 bits; Montgomery form kept
@@ -149,17 +150,18 @@ HP_D void line_store(int4* __restrict__ p, const HLine& l) {
   for (int k = 0; k < PL_Q4; k++) p[k] = make_int4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
 }
 
-// a side's raw line of this step: the walk of T (WALK) or the table entry (TABLE)
-template <class G, bool WALK, bool DBL, class ST>
-HP_D HLine side_raw(const PairSide& s, ST& st, int step) {
+// a side's raw line of this step: the walk of T (WALK; SIDE's T comes from and goes back to the
+// parking hook pk) or the table entry (TABLE)
+template <class G, bool WALK, bool DBL, int SIDE, class ST, class PK>
+HP_D HLine side_raw(const PairSide& s, ST& st, int step, const PK& pk) {
   if constexpr (!WALK) {
     return line_load(s.lines + line_at(st.q * PAIR_STEPS + step));
   } else if constexpr (DBL) {
-    return G::dbl_step(st.T);
+    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HP_L { return G::dbl_step(T); });
   } else {
     Fp xQ, yQ;
     side_q(s, st, xQ, yQ);
-    return G::add_step(st.T, xQ, yQ);
+    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HP_L { return G::add_step(T, xQ, yQ); });
   }
 }
 
@@ -235,6 +237,11 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
     if (G::leader() && a.verdict) a.verdict[i] = 0;
     return;
   }
+  // T and P wait in the stash between their uses (LanePair; the first stash12 comes after the loop).
+  // Lanes that left above never touch it.
+  const typename G::template Park<W1, W2, GEN> pk(stash + threadIdx.x);
+  pk.init(A, B);
+  constexpr bool WF = !W1 && W2;  // TABLE / WALK: a width may walk side B first
   H12 f = h12_one();
   int step = 0;
 #pragma unroll 1
@@ -243,15 +250,17 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
     if (b != 62) f = h12_sqr<G>(f);
     {
       HLine la, lb;
-      G::template lines_at_p<G1, G2>([&]() HP_L { return side_raw<G, W1, true>(a.s1, A, step); },
-                                     [&]() HP_L { return side_raw<G, W2, true>(a.s2, B, step); }, A, B, neg2, la, lb);
+      G::template lines_at_p<G1, G2, WF>([&]() HP_L { return side_raw<G, W1, true, 0>(a.s1, A, step, pk); },
+                                         [&]() HP_L { return side_raw<G, W2, true, 1>(a.s2, B, step, pk); }, A, B, neg2,
+                                         la, lb, pk);
       f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
     }
     step++;
     if ((hb::X_ABS >> b) & 1) {
       HLine la, lb;
-      G::template lines_at_p<G1, G2>([&]() HP_L { return side_raw<G, W1, false>(a.s1, A, step); },
-                                     [&]() HP_L { return side_raw<G, W2, false>(a.s2, B, step); }, A, B, neg2, la, lb);
+      G::template lines_at_p<G1, G2, WF>([&]() HP_L { return side_raw<G, W1, false, 0>(a.s1, A, step, pk); },
+                                         [&]() HP_L { return side_raw<G, W2, false, 1>(a.s2, B, step, pk); }, A, B, neg2,
+                                         la, lb, pk);
       f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
       step++;
     }

@@ -643,6 +643,122 @@ HP_D Fp side_yP(const ST& st, bool negate) {
   return GEN ? (negate ? fp_neg(fp_const(hb::G1Y_M)) : fp_const(hb::G1Y_M)) : st.yP;
 }
 
+// ---------------------------------------------------------------- Miller-loop parking
+// A width's parking hook, G::Park<W1, W2, GEN>: where a WALK side's T and a read side's P wait while
+// f is squared and multiplied by the lines, which is about three quarters of a Miller step and uses
+// neither.  lane_verify (pair_side.hpp) makes one per check over the lane's column of the
+// workgroup's LDS stash, calls init() once both sides are initialised, walks T through walk() and
+// hands the hook to lines_at_p for P.  NoPark leaves everything in the sides' registers.
+struct NoPark {
+  HP_D explicit NoPark(uint32_t*) {}
+  template <class ST>
+  HP_D void init(const ST&, const ST&) const {}
+  // f(T): one walk step of side SIDE (0 = A, 1 = B), which returns its raw line
+  template <int SIDE, class ST, class F>
+  HP_D HLine walk(ST& st, const F& f) const { return f(st.T); }
+  template <int SIDE, class ST>
+  HP_D Fp xP(const ST& st) const { return st.xP; }
+  template <int SIDE, class ST>
+  HP_D Fp yP(const ST& st) const { return st.yP; }
+};
+
+// The lane pair's: the Miller loop never touches the stash of the final exponentiation (the first
+// stash12 comes after the loop), so the lane's column holds T and P as plain 32-bit words, limbs as
+// they are -- word k at col[k * 256], a ds_read_b32 / ds_write_b32 per limb with the wave's lanes on
+// consecutive banks.  Each lane reads only what it wrote: no barrier.  First fit into the
+// PARK_WORDS words in the order T of side B, T of side A, P of side A, P of side B; what does not
+// fit stays in the side's registers (slot -1):
+//   TABLE / WALK (either order) with a generator side   T + P = 70 words
+//   TABLE / TABLE, both P read                          P + P = 56
+//   WALK / WALK                                         side B's T + one P = 70; side A's T stays
+// The accesses are volatile: the calls between a store and its load have no memory effects, so the
+// compiler would forward the stored registers to the load, and hoist P's loads out of the loop --
+// that is, keep all of it in registers across the calls and spill it to scratch as before.
+constexpr int PARK_WORDS = 72;  // a lane's column of the stash (pair_side.hpp STASH_WORDS)
+constexpr int park_fit(int used, bool need, int words) { return need && used + words <= PARK_WORDS ? used : -1; }
+typedef volatile __attribute__((address_space(3))) uint32_t* ParkCol;
+
+HP_D void park_put(ParkCol c, int slot, const Fp& a) {
+#pragma unroll
+  for (int i = 0; i < NL; i++) c[(slot + i) * 256] = (uint32_t)a.l[i];
+}
+HP_D Fp park_get(ParkCol c, int slot) {
+  Fp r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.l[i] = (int32_t)c[(slot + i) * 256];
+  return r;
+}
+
+template <bool W1, bool W2, int GEN>
+struct PairPark {
+  static constexpr int TW = 3 * NL, PW = 2 * NL;
+  static constexpr int T_B = park_fit(0, W2, TW);
+  static constexpr int U1 = T_B < 0 ? 0 : TW;
+  static constexpr int T_A = park_fit(U1, W1, TW);
+  static constexpr int U2 = U1 + (T_A < 0 ? 0 : TW);
+  static constexpr int P_A = park_fit(U2, GEN != 1, PW);
+  static constexpr int U3 = U2 + (P_A < 0 ? 0 : PW);
+  static constexpr int P_B = park_fit(U3, GEN != 2, PW);
+  template <int SIDE>
+  static constexpr int t_slot() { return SIDE == 0 ? T_A : T_B; }
+  template <int SIDE>
+  static constexpr int p_slot() { return SIDE == 0 ? P_A : P_B; }
+
+  ParkCol col;
+  HP_D explicit PairPark(uint32_t* c) : col((ParkCol)c) {}
+
+  template <int SIDE>
+  HP_D void put_T(const HProj& T) const {
+    park_put(col, t_slot<SIDE>(), T.x);
+    park_put(col, t_slot<SIDE>() + NL, T.y);
+    park_put(col, t_slot<SIDE>() + 2 * NL, T.z);
+  }
+  template <int SIDE, class ST>
+  HP_D void init_side(const ST& st) const {
+    if constexpr (t_slot<SIDE>() >= 0) put_T<SIDE>(st.T);
+    if constexpr (p_slot<SIDE>() >= 0) {
+      park_put(col, p_slot<SIDE>(), st.xP);
+      park_put(col, p_slot<SIDE>() + NL, st.yP);
+    }
+  }
+  template <class ST>
+  HP_D void init(const ST& A, const ST& B) const {
+    init_side<0>(A);
+    init_side<1>(B);
+  }
+  template <int SIDE, class ST, class F>
+  HP_D HLine walk(ST& st, const F& f) const {
+    if constexpr (t_slot<SIDE>() < 0) {
+      return f(st.T);
+    } else {
+      HProj T;  // in the order the doubling step takes them up
+      T.z = park_get(col, t_slot<SIDE>() + 2 * NL);
+      T.y = park_get(col, t_slot<SIDE>() + NL);
+      T.x = park_get(col, t_slot<SIDE>());
+      const HLine l = f(T);
+      put_T<SIDE>(T);
+      return l;
+    }
+  }
+  template <int SIDE, class ST>
+  HP_D Fp xP(const ST& st) const {
+    if constexpr (p_slot<SIDE>() < 0) return st.xP; else return park_get(col, p_slot<SIDE>());
+  }
+  template <int SIDE, class ST>
+  HP_D Fp yP(const ST& st) const {
+    if constexpr (p_slot<SIDE>() < 0) return st.yP; else return park_get(col, p_slot<SIDE>() + NL);
+  }
+};
+
+// A/B switches of the lane-pair Miller loop (profiles/r18): HP_PARK = the PairPark above, else
+// NoPark; HP_WALK_FIRST = a TABLE / WALK check walks its WALK side before it fetches the table's line
+#ifndef HP_PARK
+#define HP_PARK 1
+#endif
+#ifndef HP_WALK_FIRST
+#define HP_WALK_FIRST 1
+#endif
+
 // ---------------------------------------------------------------- the lane pair as a width policy
 // What the shared Fp12 operations above and the kernel body and final exponentiation of
 // pair_side.hpp ask of a width.  The lane pair runs every product on its own, one after the other.
@@ -679,22 +795,41 @@ struct LanePair {
   static HP_D H12 frob1(const H12& f) { return h12_frob1(f); }
   static HP_D H12 frob2(const H12& f) { return h12_frob2(f); }
 
-  // a side's line (c0, c1, c4) evaluated at its P: (c0, c1 xP, c4 yP), or 1 for an inactive pair
-  template <bool GEN, class ST>
-  static HP_D HLine line_at_p(const HLine& l, const ST& st, bool negate) {
+#if HP_PARK
+  template <bool W1, bool W2, int GEN>
+  using Park = PairPark<W1, W2, GEN>;
+#else
+  template <bool W1, bool W2, int GEN>
+  using Park = NoPark;
+#endif
+
+  // a side's line (c0, c1, c4) evaluated at its P: (c0, c1 xP, c4 yP), or 1 for an inactive pair.
+  // P comes from the parking hook (the side's registers, or the stash), each coordinate as its
+  // product is due.
+  template <bool GEN, int SIDE, class ST, class PK>
+  static HP_D HLine line_at_p(const HLine& l, const ST& st, bool negate, const PK& pk) {
     HLine e;
     e.c0 = st.act ? l.c0 : h_one();
-    e.c1 = st.act ? fp_mul(l.c1, side_xP<GEN>(st)) : fp_zero();
-    e.c4 = st.act ? fp_mul(l.c4, side_yP<GEN>(st, negate)) : fp_zero();
+    const Fp c1 = fp_mul(l.c1, GEN ? side_xP<true>(st) : pk.template xP<SIDE>(st));
+    e.c1 = st.act ? c1 : fp_zero();
+    const Fp c4 = fp_mul(l.c4, GEN ? side_yP<true>(st, negate) : pk.template yP<SIDE>(st));
+    e.c4 = st.act ? c4 : fp_zero();
     return e;
   }
-  // both sides' lines of a step: raw_a() / raw_b() walk the side's T or read its table.  Side A is
-  // walked and evaluated before side B is walked.
-  template <bool G1, bool G2, class RA, class RB, class ST>
+  // both sides' lines of a step: raw_a() / raw_b() walk the side's T or read its table.  A side is
+  // walked and evaluated before the other one is walked: side A first, or, WALK_FIRST (TABLE / WALK),
+  // side B, so that the table's evaluated line is not live across the walk.  la and lb are the same
+  // values either way.
+  template <bool G1, bool G2, bool WALK_FIRST, class RA, class RB, class ST, class PK>
   static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
-                              HLine& lb) {
-    la = line_at_p<G1>(raw_a(), A, false);
-    lb = line_at_p<G2>(raw_b(), B, neg2);
+                              HLine& lb, const PK& pk) {
+    if constexpr (WALK_FIRST && HP_WALK_FIRST) {
+      lb = line_at_p<G2, 1>(raw_b(), B, neg2, pk);
+      la = line_at_p<G1, 0>(raw_a(), A, false, pk);
+    } else {
+      la = line_at_p<G1, 0>(raw_a(), A, false, pk);
+      lb = line_at_p<G2, 1>(raw_b(), B, neg2, pk);
+    }
   }
 };
 

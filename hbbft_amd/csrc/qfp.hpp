@@ -184,6 +184,8 @@ struct LaneQuad {
   static HP_D bool leader() { return (threadIdx.x & 3) == 0; }
   static HP_D bool value_writer() { return !q_hi(); }  // pair 0
   using Walk = HJac;
+  template <bool W1, bool W2, int GEN>
+  using Park = NoPark;  // T and P stay in registers
   static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_q(T); }
   static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_q(T, xQ, yQ); }
 
@@ -218,9 +220,9 @@ struct LaneQuad {
     e.c4 = st.act ? c4 : fp_zero();
     return e;
   }
-  template <bool G1, bool G2, class RA, class RB, class ST>
+  template <bool G1, bool G2, bool WALK_FIRST, class RA, class RB, class ST>
   static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
-                              HLine& lb) {
+                              HLine& lb, const NoPark&) {
     la = line_at_p<G1>(raw_a(), A, false);
     lb = line_at_p<G2>(raw_b(), B, neg2);
   }
