@@ -253,7 +253,9 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
       G::template lines_at_p<G1, G2, WF>([&]() HP_L { return side_raw<G, W1, true, 0>(a.s1, A, step, pk); },
                                          [&]() HP_L { return side_raw<G, W2, true, 1>(a.s2, B, step, pk); }, A, B, neg2,
                                          la, lb, pk);
-      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
+      // b == 62: f is still 1, and a width may take the line product as f
+      constexpr bool FL = G::template first_line<W1, W2>();
+      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4, FL && b == 62);
     }
     step++;
     if ((hb::X_ABS >> b) & 1) {

@@ -279,6 +279,10 @@ HP_D Fp h_inv_vartime(const Fp& a) {
 // <= 3.  The quotient comes from the top limb alone (as in fp_reduce); the lower limbs' excess moves
 // the value by < 2^368 < 2^-12 p, so the output is normalised and in (-p/1000, p + p/1000) --
 // inside (R).  Replaces a normalisation pass per sum plus fp_reduce's pass.
+// h6_mul6 and the scaled h6_mul_12 widen the contract as h_dbl_step_h's <12, 0> does: <3, 0>, <6, 0>
+// and <1, 6> with |t_i| < 2^31, |a_i| < 2^31 and |M t + K a| < 64p.  The int64 terms stay below
+// 7 x 2^31, the top limb of the sum below 64 x 1.7 x 2^16 < 2^23 (the quotient estimate's range), and
+// the lower limbs' excess below 2^34 x 2^336 < p / 1000: the output bound is the same.
 template <int M, int K>
 HP_D Fp fp_red_mk(const Fp& t, const Fp& a) {
   const int64_t top = (int64_t)t.l[NL - 1] * M + (int64_t)K * a.l[NL - 1];
@@ -295,6 +299,31 @@ HP_D Fp fp_red_mk(const Fp& t, const Fp& a) {
   return r;
 }
 HP_D Fp fp_red_l(const Fp& t) { return fp_red_mk<1, 0>(t, t); }
+// reduce(a + 2 b + 4 c) in one carry pass, a, b, c normalised with |.| < 4p: the sum is < 28p with
+// limbs < 7 x 2^28, so the top limb is < 2^22 and the lower limbs' excess < 2^368, as in fp_red_mk;
+// output normalised in (-p/1000, p + p/1000)
+HP_D Fp fp_red_124(const Fp& a, const Fp& b, const Fp& c) {
+  const int32_t top = a.l[NL - 1] + 2 * b.l[NL - 1] + 4 * c.l[NL - 1];
+  const int32_t q = (int32_t)(((int64_t)top * QINV) >> 32);
+  Fp r;
+  int64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < NL - 1; i++) {
+    acc += (int64_t)(a.l[i] + 2 * b.l[i] + 4 * c.l[i]) - (int64_t)q * (int32_t)P_L[i];
+    r.l[i] = (int32_t)acc & MASK28;
+    acc >>= 28;
+  }
+  r.l[NL - 1] = (int32_t)(acc + top - (int64_t)q * (int32_t)P_L[NL - 1]);
+  return r;
+}
+// a + k1 b + k2 c for small signed k (1 + |k1| + |k2| <= 7), normalised
+HP_D Fp fp_lin3(const Fp& a, int k1, const Fp& b, int k2, const Fp& c) {
+  Fp r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.l[i] = a.l[i] + k1 * b.l[i] + k2 * c.l[i];
+  fp_norm(r);
+  return r;
+}
 // own component of s + xi t without normalising (|s_i| + 2 |t_i| < 2^31)
 HP_D Fp h_add_xi_l(const Fp& s, const Fp& t) {
   const int32_t sm = lp_even() ? -1 : 0;
@@ -347,6 +376,55 @@ HP_D H6 h6_mul(const H6& a, const H6& b) {
   const Fp c2 = fp_red_l(fp_addl(fp_sub2l(h_mul(fp_addl(a.c0, a.c2), fp_add(b.c0, b.c2)), v0, v2), v1));
   return {c0, c1, c2};
 }
+// 6 a b by Toom-Cook-3: five Fp2 products, on the evaluations at 0, 1, -1, 2 and infinity, instead
+// of Karatsuba's six.  The interpolation has integer coefficients only because it stops at 6 a b:
+//   P0 = a0 b0, Pi = a2 b2, P1 = a(1) b(1), Pm = a(-1) b(-1), P2 = a(2) b(2)
+//   t = P2 + 3 (P0 - P1) - Pm                      (6 a b's v^3 coefficient is t - 12 Pi)
+//   c0 = 6 P0 + xi (t - 12 Pi)            = xi t + 6 (P0 - 2 xi Pi)
+//   c1 = 3 (P1 - Pm) - t + 12 Pi + 6 xi Pi = 3 (P1 - Pm) - t + 6 (2 Pi + xi Pi)
+//   c2 = 3 (P1 + Pm - 2 P0 - 2 Pi)
+// The factor 6 is in Fp, so a Miller-loop value that carries it (any power of it) has the same
+// final exponentiation: c^(p^6 - 1) = 1.  Only h12_sqr and h12_mul_lines use this product.
+//
+// Contract: a normalised, |a_i| < 4p; b normalised, |b0| + 2 |b1| + 4 |b2| < 16p (|b_i| < 2.28p);
+// outputs reduced.  Operands of the products: a(1) = (a0 + a2) + a1 lazy, limbs < 2^29, < 12p;
+// a(-1) lazy, |limb| < 2^28, < 12p; a(2) reduced in its own pass (28p before it); b(1), b(-1) < 7p
+// and b(2) < 16p normalised.  So every product is normalised (limbs 0..12 in [0, 2^28)) and in
+// (-0.2p, 1.4p): 1.25p + 2 x 12p x 7p x 2^-392 < 1.33p.
+// int32: P1 + Pm - 2 P0 - 2 Pi in (-2^30, 2^29); m = 3 (P0 - P1) - Pm and t = P2 + m in (-2^30, 2^30),
+// xi t in (-2^31, 2^31); 3 (P1 - Pm) - t in +-7 x 2^28; P0 - 2 xi Pi in +-5 x 2^28; 2 Pi + xi Pi in
+// (-2^28, 2^30).  Values into the passes, with |P| < 1.33p: |c0| < 2 x 8 x 1.33p + 6 x 5 x 1.33p =
+// 61.2p, |c1| < 14 x 1.33p + 6 x 4 x 1.33p = 50.6p, |c2| < 18 x 1.33p: inside fp_red_mk's 64p.
+// Register order: P1, Pm, P0, Pi, then c2 and the four sums that the last two outputs need, then
+// P2: five values are live beside the operands across the last product, as in h6_mul.
+HP_D H6 h6_mul6(const H6& a, const H6& b) {
+  Fp c2, m, e, k, h;
+  {
+    const Fp sa = fp_add(a.c0, a.c2);
+    const Fp p1 = h_mul(fp_addl(sa, a.c1), fp_lin3(b.c0, 1, b.c1, 1, b.c2));
+    const Fp pm = h_mul(fp_subl(sa, a.c1), fp_lin3(b.c0, -1, b.c1, 1, b.c2));
+    const Fp p0 = h_mul(a.c0, b.c0);
+    const Fp pi = h_mul(a.c2, b.c2);
+    const Fp xpi = h_xi_l(pi);
+    Fp w;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+      w.l[i] = p1.l[i] + pm.l[i] - 2 * p0.l[i] - 2 * pi.l[i];
+      m.l[i] = 3 * (p0.l[i] - p1.l[i]) - pm.l[i];
+      e.l[i] = p1.l[i] - pm.l[i];
+      k.l[i] = p0.l[i] - 2 * xpi.l[i];
+      h.l[i] = 2 * pi.l[i] + xpi.l[i];
+    }
+    c2 = fp_red_mk<3, 0>(w, w);
+  }
+  const Fp t = fp_addl(h_mul(fp_red_124(a.c0, a.c1, a.c2), fp_lin3(b.c0, 2, b.c1, 4, b.c2)), m);
+  const Fp c0 = fp_red_mk<1, 6>(h_xi_l(t), k);
+  Fp g;
+#pragma unroll
+  for (int i = 0; i < NL; i++) g.l[i] = 3 * e.l[i] - t.l[i];
+  const Fp c1 = fp_red_mk<1, 6>(g, h);
+  return {c0, c1, c2};
+}
 HP_D H6 h6_inv(const H6& a) {
   const Fp c0 = fp_reduce(fp_sub(h_sqr(a.c0), h_mul_xi(h_mul(a.c1, a.c2))));
   const Fp c1 = fp_reduce(fp_sub(h_mul_xi(h_sqr(a.c2)), h_mul(a.c0, a.c1)));
@@ -371,13 +449,19 @@ HP_D H12 h12_kcomb(const H6& t0, const H6& t1, const H6& s) {
 }
 
 // x (b1 v + b2 v^2): c0 = xi (a1 b2 + a2 b1), c1 = a0 b1 + xi a2 b2, c2 = a0 b2 + a1 b1 (5 products);
-// outputs reduced
+// outputs reduced.  S: the product comes out times S (1, or 6 beside h6_mul6), multiplied inside the
+// carry passes: the sums are < 3 x 2^28 per limb and < 7.8p (xi of three products of < 1.3p), so
+// 6 times them is < 47p, inside fp_red_mk's widened contract.
+template <int S = 1>
 HP_D H6 h6_mul_12(const H6& x, const Fp& b1, const Fp& b2) {
   const Fp u = h_mul(x.c1, b1);
   const Fp w = h_mul(x.c2, b2);
-  const Fp c0 = fp_red_l(h_xi_l(fp_sub2l(h_mul(fp_addl(x.c1, x.c2), fp_add(b1, b2)), u, w)));
-  const Fp c1 = fp_red_l(h_add_xi_l(h_mul(x.c0, b1), w));
-  const Fp c2 = fp_red_l(fp_addl(h_mul(x.c0, b2), u));
+  const Fp d0 = h_xi_l(fp_sub2l(h_mul(fp_addl(x.c1, x.c2), fp_add(b1, b2)), u, w));
+  const Fp c0 = fp_red_mk<S, 0>(d0, d0);
+  const Fp d1 = h_add_xi_l(h_mul(x.c0, b1), w);
+  const Fp c1 = fp_red_mk<S, 0>(d1, d1);
+  const Fp d2 = fp_addl(h_mul(x.c0, b2), u);
+  const Fp c2 = fp_red_mk<S, 0>(d2, d2);
   return {c0, c1, c2};
 }
 
@@ -406,11 +490,18 @@ HP_D H12 h12_mul(const H12& a, const H12& b) {
   return h12_kcomb(t0, t1, s);
 }
 // complex squaring: t = a0 a1, s = (a0 + a1)(a0 + v a1); c0 = s - t - v t, c1 = 2 t (one pass each)
+// Miller loop only: the value is G::MILLER_SCALE times the square.  A width with a scale other than
+// 1 has the scaled products mul6x2_s, mul6x2_12_s and mul6_s beside the exact ones; every formula
+// here and in h12_mul_lines is linear in its Fp6 products, so the factor carries through.
 template <class G>
 HP_D H12 h12_sqr(const H12& a) {
   H6 t, s;
-  G::mul6x2(a.c0, a.c1, [&]() HP_L { return h6_add(a.c0, a.c1); },
-            [&]() HP_L { return h6_red(h6_add(a.c0, h6_mul_v(a.c1))); }, t, s);
+  const auto a1 = [&]() HP_L { return h6_add(a.c0, a.c1); };
+  const auto b1 = [&]() HP_L { return h6_red(h6_add(a.c0, h6_mul_v(a.c1))); };
+  if constexpr (G::MILLER_SCALE == 1)
+    G::mul6x2(a.c0, a.c1, a1, b1, t, s);
+  else
+    G::mul6x2_s(a.c0, a.c1, a1, b1, t, s);
   return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
            fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
           {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
@@ -418,15 +509,25 @@ HP_D H12 h12_sqr(const H12& a) {
 // f * (la * lb) for two sparse lines (c0 + c1 w^2 + c4 w^3 each, normalised, < 2p): the line
 // product L = (C0, C1) has C1.c0 = 0 (6 products), then one Karatsuba step over Fp6 with the sparse
 // C1 -- on the lane pair 6 + 5 + 6 products, 23 in all instead of 2 x 13 for one line at a time.
+// Miller loop only: G::MILLER_SCALE times the product (see h12_sqr).  first: f is the 1 that the
+// Miller loop starts from (lane_verify, where G::first_line says so): the line product itself is
+// the new f, whatever f holds.
 template <class G>
 HP_D H12 h12_mul_lines(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1,
-                       const Fp& b4) {
+                       const Fp& b4, bool first = false) {
   H6 C0, t0, t1;
   Fp c11, c12;
   G::line_product(a0, a1, a4, b0, b1, b4, C0, c11, c12);
-  G::mul6x2_12(f.c0, C0, f.c1, c11, c12, t0, t1);
-  const H6 s = G::mul6(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
-  return h12_kcomb(t0, t1, s);
+  if (first) return {C0, {h_zero(), c11, c12}};
+  if constexpr (G::MILLER_SCALE == 1) {
+    G::mul6x2_12(f.c0, C0, f.c1, c11, c12, t0, t1);
+    const H6 s = G::mul6(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
+    return h12_kcomb(t0, t1, s);
+  } else {
+    G::mul6x2_12_s(f.c0, C0, f.c1, c11, c12, t0, t1);
+    const H6 s = G::mul6_s(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
+    return h12_kcomb(t0, t1, s);
+  }
 }
 template <class G>
 HP_D H12 h12_inv(const H12& a) {
@@ -758,6 +859,15 @@ struct PairPark {
 #ifndef HP_WALK_FIRST
 #define HP_WALK_FIRST 1
 #endif
+// (profiles/r19): HP_TOOM = the Miller loop's full Fp6 products are h6_mul6 and f carries powers of
+// 6, else Karatsuba and no factor; HP_FIRST_LINE = the first step's line product is taken as f
+// instead of being multiplied into f = 1: 1 = in the checks with a WALK side, 2 = in all of them
+#ifndef HP_TOOM
+#define HP_TOOM 1
+#endif
+#ifndef HP_FIRST_LINE
+#define HP_FIRST_LINE 1
+#endif
 
 // ---------------------------------------------------------------- the lane pair as a width policy
 // What the shared Fp12 operations above and the kernel body and final exponentiation of
@@ -779,6 +889,25 @@ struct LanePair {
   static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
     r0 = h6_mul(a0, b0);
     r1 = h6_mul_12(a1, c1, c2);  // 5 products
+  }
+  // The Miller loop's products (h12_sqr, h12_mul_lines) come out times MILLER_SCALE, a factor in Fp
+  // that the final exponentiation removes: 6 with the five-product h6_mul6, and the sparse product
+  // brought to the same factor in its carry passes.  h12_mul, h12_inv and the whole final
+  // exponentiation keep the exact products above: a cyclotomic element must not be scaled.
+  static constexpr int MILLER_SCALE = HP_TOOM ? 6 : 1;
+  // the first step's line product is taken as f (17 products less) in the checks that walk a side;
+  // a TABLE / TABLE check was slower with it (profiles/r19)
+  template <bool W1, bool W2>
+  static constexpr bool first_line() { return HP_FIRST_LINE == 2 || (HP_FIRST_LINE == 1 && (W1 || W2)); }
+  static HP_D H6 mul6_s(const H6& a, const H6& b) { return h6_mul6(a, b); }
+  template <class A1, class B1>
+  static HP_D void mul6x2_s(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    r0 = h6_mul6(a0, b0);
+    r1 = h6_mul6(h6_of(a1), h6_of(b1));
+  }
+  static HP_D void mul6x2_12_s(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
+    r0 = h6_mul6(a0, b0);
+    r1 = h6_mul_12<6>(a1, c1, c2);
   }
   // each coefficient is reduced (one carry pass) as soon as its products exist
   static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,

@@ -189,6 +189,9 @@ struct LaneQuad {
   static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_q(T); }
   static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_q(T, xQ, yQ); }
 
+  static constexpr int MILLER_SCALE = 1;  // exact Karatsuba products in the Miller loop too
+  template <bool W1, bool W2>
+  static constexpr bool first_line() { return false; }
   static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul_q(a, b); }
   template <class A1, class B1>
   static HP_D void mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
