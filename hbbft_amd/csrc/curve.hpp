@@ -16,9 +16,7 @@ HB_HD Fp fdbl(const Fp& a) { return fp_dbl(a); }
 HB_HD Fp fneg(const Fp& a) { return fp_neg(a); }
 HB_HD Fp fmul(const Fp& a, const Fp& b) { return fp_mul(a, b); }
 HB_HD Fp fsqr(const Fp& a) { return fp_sqr(a); }
-HB_HD Fp finv(const Fp& a) { return fp_inv(a); }
 HB_HD bool fisz(const Fp& a) { return fp_is_zero(a); }
-HB_HD Fp fsel(bool c, const Fp& a, const Fp& b) { return fp_sel(c, a, b); }
 HB_HD void fset_one(Fp& a) { a = fp_one(); }
 HB_HD void fset_zero(Fp& a) { a = fp_zero(); }
 
@@ -28,9 +26,7 @@ HB_HD Fp2 fdbl(const Fp2& a) { return f2_dbl(a); }
 HB_HD Fp2 fneg(const Fp2& a) { return f2_neg(a); }
 HB_HD Fp2 fmul(const Fp2& a, const Fp2& b) { return f2_mul(a, b); }
 HB_HD Fp2 fsqr(const Fp2& a) { return f2_sqr(a); }
-HB_HD Fp2 finv(const Fp2& a) { return f2_inv(a); }
 HB_HD bool fisz(const Fp2& a) { return f2_is_zero(a); }
-HB_HD Fp2 fsel(bool c, const Fp2& a, const Fp2& b) { return f2_sel(c, a, b); }
 HB_HD void fset_one(Fp2& a) { a = f2_one(); }
 HB_HD void fset_zero(Fp2& a) { a = f2_zero(); }
 

@@ -545,7 +545,6 @@ inline Fq fq_sub(const Fq& a, const Fq& b) {
   return fq_sub_portable(a, b);
 #endif
 }
-inline Fq fq_dbl(const Fq& a) { return fq_add(a, a); }
 inline Fq fq_neg(const Fq& a) { return fq_is_zero(a) ? a : fq_sub(fq_zero(), a); }
 inline Fq fq_mul(const Fq& a, const Fq& b) {
 #if defined(__x86_64__)
@@ -664,7 +663,6 @@ inline Fq2 f2_sqr(const Fq2& a) {
   const Fq m = fq_mul(a.c0, a.c1);
   return {s, fq_add(m, m)};
 }
-inline Fq2 f2_mul_fq(const Fq2& a, const Fq& s) { return {fq_mul(a.c0, s), fq_mul(a.c1, s)}; }
 inline bool f2_is_zero(const Fq2& a) { return fq_is_zero(a.c0) && fq_is_zero(a.c1); }
 inline bool f2_eq(const Fq2& a, const Fq2& b) { return fq_eq(a.c0, b.c0) && fq_eq(a.c1, b.c1); }
 inline Fq2 f2_zero() { return {fq_zero(), fq_zero()}; }

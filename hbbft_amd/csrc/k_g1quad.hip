@@ -26,13 +26,8 @@ constexpr int Q_FB_WINDOWS = 32, Q_FB_ROW = 256, Q_G1_WORDS = 24;
 __device__ __forceinline__ QJ g1q_mul_small(const QJ& p, uint32_t k) {
   if (k == 0) return qj_inf();
   const int top = 31 - __builtin_clz(k);
-  QJ acc = p;
-#pragma unroll 1
-  for (int i = top - 1; i >= 0; i--) {
-    acc = g1q_dbl(acc);
-    if ((k >> i) & 1) acc = g1q_add(acc, p);
-  }
-  return acc;
+  return dbl_and_add(p, k, top - 1, [](const QJ& a) HS_LAMBDA { return g1q_dbl(a); },
+                     [&](const QJ& a) HS_LAMBDA { return g1q_add(a, p); });
 }
 
 // P == Q as group elements, 2 rounds
@@ -191,6 +186,7 @@ constexpr int G1Q_Q = 64;  // quads per workgroup
 __device__ __forceinline__ QJ g1q_mul_affine(const Fp& x, const Fp& y, bool inf, uint32_t k) {
   if (inf || k == 0) return qj_inf();
   const int top = 31 - __builtin_clz(k);
+  // written out: through dbl_and_add this loop compiles to other registers in k_interp_g1q
   QJ acc{x, y, fp_one()};
 #pragma unroll 1
   for (int i = top - 1; i >= 0; i--) {

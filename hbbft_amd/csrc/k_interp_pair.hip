@@ -28,58 +28,11 @@ constexpr int IP_Q = IP_THREADS / 4;     // lane quads per workgroup (power of t
 constexpr int IP_WORDS = 3 * NL;         // one lane's Jacobian point (x, y, z own components)
 
 // k * (x, y) for a 32-bit k, double-and-add from the top set bit (jac_mul_affine)
-HP_D HJac hj_mul_affine(const Fp& x, const Fp& y, bool inf, uint32_t k) {
-  HJac acc = hj_zero();
-  if (inf || k == 0) return acc;
-  const int top = 31 - __builtin_clz(k);
-  acc = {x, y, h_one()};
-#pragma unroll 1
-  for (int i = top - 1; i >= 0; i--) {
-    acc = hj_dbl(acc);
-    if ((k >> i) & 1) acc = hj_add_affine(acc, x, y);
-  }
-  return acc;
-}
-
-// hj_add in 9 rounds (Z3 = 2 Z1 Z2 H)
-HP_D HJac qj_add(const HJac& p, const HJac& q) {
-  if (hj_is_zero(p)) return q;
-  if (hj_is_zero(q)) return p;
-  Fp Z1Z1, Z2Z2, U1, U2, YZ1, YZ2, S1, S2;
-  q_sqr(p.z, q.z, Z1Z1, Z2Z2);
-  q_mul(p.x, Z2Z2, q.x, Z1Z1, U1, U2);
-  q_mul(p.y, q.z, q.y, p.z, YZ1, YZ2);
-  q_mul(YZ1, Z2Z2, YZ2, Z1Z1, S1, S2);
-  const Fp H = fp_reduce(fp_sub(U2, U1));
-  const Fp rr = fp_reduce(fp_lin(2, S2, -2, S1));
-  if (h_is_zero(H)) {
-    if (h_is_zero(rr)) return qj_dbl(p);
-    return hj_zero();
-  }
-  Fp I, RR, J, V, EV, SJ, Z12, ZH;
-  q_sqr(fp_add(H, H), rr, I, RR);
-  q_mul(H, I, U1, I, J, V);
-  HJac r;
-  r.x = fp_reduce(fp_sub(fp_sub(RR, J), fp_add(V, V)));
-  q_mul(rr, fp_sub(V, r.x), S1, J, EV, SJ);
-  r.y = fp_reduce(fp_sub(EV, fp_add(SJ, SJ)));
-  Z12 = h_mul(p.z, q.z);
-  ZH = h_mul(Z12, H);
-  r.z = fp_reduce(fp_add(ZH, ZH));
-  return r;
-}
-
 HP_D HJac qj_mul_affine(const Fp& x, const Fp& y, bool inf, uint32_t k) {
-  HJac acc = hj_zero();
-  if (inf || k == 0) return acc;
+  if (inf || k == 0) return hj_zero();
   const int top = 31 - __builtin_clz(k);
-  acc = {x, y, h_one()};
-#pragma unroll 1
-  for (int i = top - 1; i >= 0; i--) {
-    acc = qj_dbl(acc);
-    if ((k >> i) & 1) acc = qj_add_affine(acc, x, y);
-  }
-  return acc;
+  return dbl_and_add(HJac{x, y, h_one()}, k, top - 1, [](const HJac& a) HS_LAMBDA { return qj_dbl(a); },
+                     [&](const HJac& a) HS_LAMBDA { return qj_add_affine(a, x, y); });
 }
 
 // psi on own components: psi(x) = conj(x) * (0 + c u) -> (x1 c, x0 c); psi(y) = conj(y) * c2
@@ -173,7 +126,7 @@ __global__ void __launch_bounds__(64) k_interp_join(int ncomb, const int32_t* __
   const Fp zi = h_inv_vartime(fp_reduce(r.z));
   const Fp zi2 = h_sqr(zi);
   Fp xa, zi3;
-  q_mul(r.x, zi2, zi2, zi, xa, zi3);
+  h_mul2(r.x, zi2, zi2, zi, xa, zi3);
   const Fp ya = h_mul(r.y, zi3);
   if (!q_hi()) {
     fp_to_words(xa, o);

@@ -6,15 +6,9 @@
 // the byte-level flag checks and the big-endian -> little-endian word reversal (wire.hpp).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "curve.hpp"
 #include "wire.hpp"
 #include "wire_root.hpp"
-
-#ifndef HBH_G1_WAVES_PER_SIMD
-#define HBH_G1_WAVES_PER_SIMD 2  // A/B: 1 (512 registers, no spills, half the waves in flight)
-#endif
 
 namespace hb {
 
@@ -83,9 +77,10 @@ __device__ __forceinline__ bool g1_in_subgroup(const Fp& x, const Fp& y) {
 // points are two waves per SIMD instead of one (the decoder is issue-bound at one wave per SIMD:
 // profiles/r06/c3_wire/decode_pmc_sq.csv, ~5.1 cycles per VALU instruction).  When rhs is not a
 // square, P' lies on a twist and wave 1's answer is discarded with the point.
-__global__ void __launch_bounds__(128, HBH_G1_WAVES_PER_SIMD) k_g1_decompress(int n, const uint32_t* __restrict__ xw,
-                                                       const uint8_t* __restrict__ flags, uint32_t* __restrict__ out,
-                                                       uint8_t* __restrict__ ok) {
+// Two waves per SIMD; the alternative is 1 (512 registers, no spills, half the waves in flight).
+__global__ void __launch_bounds__(128, 2) k_g1_decompress(int n, const uint32_t* __restrict__ xw,
+                                                          const uint8_t* __restrict__ flags, uint32_t* __restrict__ out,
+                                                          uint8_t* __restrict__ ok) {
   __shared__ uint8_t in_group[64];
   const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
   const int i = blockIdx.x * 64 + lane;
@@ -135,10 +130,11 @@ __global__ void __launch_bounds__(128, HBH_G1_WAVES_PER_SIMD) k_g1_decompress(in
 // Wave 1 runs [|x|] P' (68 group operations over Fp2) while wave 0 takes the square root (two
 // (p - 3) / 4 chains); wave 0 then publishes N(y) through LDS and wave 1 finishes the comparison.
 // #E'(Fp2) = h2 r is odd, so no point has rhs = 0 (where iota would degenerate).
-template <int WPS>
-__global__ void __launch_bounds__(128, WPS) k_g2_decompress(int n, const uint32_t* __restrict__ xw,
-                                                       const uint8_t* __restrict__ flags, uint32_t* __restrict__ out,
-                                                       uint8_t* __restrict__ ok) {
+// Two waves per SIMD: 256 registers (spills) and twice the waves in flight; the alternative is one
+// wave per SIMD: 512 registers, no spills.
+__global__ void __launch_bounds__(128, 2) k_g2_decompress(int n, const uint32_t* __restrict__ xw,
+                                                          const uint8_t* __restrict__ flags, uint32_t* __restrict__ out,
+                                                          uint8_t* __restrict__ ok) {
   __shared__ uint32_t nrm[NL * 64];
   __shared__ uint8_t in_group[64];
   const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
@@ -262,17 +258,8 @@ hipError_t g1_decompress(hipStream_t s, int n, const uint32_t* xw, const uint8_t
 
 hipError_t g2_decompress(hipStream_t s, int n, const uint32_t* xw, const uint8_t* flags, void* out, uint8_t* ok) {
   if (n <= 0) return hipSuccess;
-  // one wave per SIMD: 512 registers, no spills; two: 256 registers (spills) and twice the waves in flight
-  static const int waves = [] {
-    const char* v = std::getenv("HBH_G2_DEC_WAVES");
-    return v ? std::atoi(v) : 2;
-  }();
-  if (waves == 1)
-    hipLaunchKernelGGL(hb::k_g2_decompress<1>, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, n, xw, flags,
-                       (uint32_t*)out, ok);
-  else
-    hipLaunchKernelGGL(hb::k_g2_decompress<2>, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, n, xw, flags,
-                       (uint32_t*)out, ok);
+  hipLaunchKernelGGL(hb::k_g2_decompress, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, n, xw, flags,
+                     (uint32_t*)out, ok);
   return hipGetLastError();
 }
 

@@ -41,22 +41,13 @@ __device__ __forceinline__ bool below_p(const uint32_t* x) {
 
 // [|x|] P for the quad's affine P (not infinity): one mixed addition per set bit
 __device__ __forceinline__ hbs::QJ g1q_mul_absx_affine(const hbs::Fp& x, const hbs::Fp& y) {
-  hbs::QJ acc{x, y, hbs::fp_one()};
-#pragma unroll 1
-  for (int i = 62; i >= 0; i--) {
-    acc = hbs::g1q_dbl(acc);
-    if ((hb::X_ABS >> i) & 1) acc = hbs::g1q_add_affine(acc, x, y);
-  }
-  return acc;
+  return hbs::dbl_and_add(hbs::QJ{x, y, hbs::fp_one()}, hb::X_ABS, 62,
+                          [](const hbs::QJ& a) HS_LAMBDA { return hbs::g1q_dbl(a); },
+                          [&](const hbs::QJ& a) HS_LAMBDA { return hbs::g1q_add_affine(a, x, y); });
 }
 __device__ __forceinline__ hbs::QJ g1q_mul_absx(const hbs::QJ& p) {
-  hbs::QJ acc = p;
-#pragma unroll 1
-  for (int i = 62; i >= 0; i--) {
-    acc = hbs::g1q_dbl(acc);
-    if ((hb::X_ABS >> i) & 1) acc = hbs::g1q_add(acc, p);
-  }
-  return acc;
+  return hbs::dbl_and_add(p, hb::X_ABS, 62, [](const hbs::QJ& a) HS_LAMBDA { return hbs::g1q_dbl(a); },
+                          [&](const hbs::QJ& a) HS_LAMBDA { return hbs::g1q_add(a, p); });
 }
 
 // The G1 criterion on P' = (rhs x, rhs^2): [|x|]([|x|] P') == (beta X, -Y).  xw: canonical x < p.
@@ -147,8 +138,9 @@ __global__ void __launch_bounds__(WS_THREADS) k_g2_decompress_split(int n, const
       const Fp xm = fp_from_words(xi + (lp_even() ? 0 : 12));
       const Fp rhs = fp_add(h_mul(h_sqr(xm), xm), h_const(hb::B1_M, hb::B1_M));  // b = 4 (1 + u)
       Fp X, Y;
-      q_mul(rhs, xm, rhs, rhs, X, Y);
-      HJac q{X, Y, h_one()};  // [|x|] P'
+      h_mul2(rhs, xm, rhs, rhs, X, Y);
+      // [|x|] P', written out: through dbl_and_add this loop compiles to other registers here
+      HJac q{X, Y, h_one()};
 #pragma unroll 1
       for (int b = 62; b >= 0; b--) {
         q = qj_dbl(q);
@@ -158,8 +150,8 @@ __global__ void __launch_bounds__(WS_THREADS) k_g2_decompress_split(int n, const
       const Fp cx = fp_mul(dpp_fp<DPP_SWAP>(xm), fp_const(hb::PSI_C1_C1));
       const Fp z2 = h_sqr(q.z);
       Fp tx, z3, txz, rc2;
-      q_mul(rhs, cx, z2, q.z, tx, z3);
-      q_mul(tx, z2, rhs, h_const(hb::PSI_C2_C0, hb::PSI_C2_C1), txz, rc2);
+      h_mul2(rhs, cx, z2, q.z, tx, z3);
+      h_mul2(tx, z2, rhs, h_const(hb::PSI_C2_C0, hb::PSI_C2_C1), txz, rc2);
       gx = !hj_is_zero(q) && h_is_zero(fp_sub(q.x, txz));
       w = fp_neg(h_mul(rc2, z3));
       qy = q.y;

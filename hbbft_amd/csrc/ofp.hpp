@@ -260,7 +260,6 @@ struct LaneOcto {
   static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_o(T); }
   static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_o(T, xQ, yQ); }
 
-  static constexpr int MILLER_SCALE = 1;  // exact Karatsuba products in the Miller loop too
   template <bool W1, bool W2>
   static constexpr bool first_line() { return false; }
   static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul_o(a, b); }
@@ -270,6 +269,16 @@ struct LaneOcto {
   }
   static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
     h6_mul_pair_o(a0, b0, a1, {h_zero(), c1, c2}, r0, r1);
+  }
+  static constexpr int MILLER_SCALE = 1;  // the Miller loop takes the exact Karatsuba products too
+  static HP_D H6 miller_mul6(const H6& a, const H6& b) { return mul6(a, b); }
+  template <class A1, class B1>
+  static HP_D void miller_mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    mul6x2(a0, b0, a1, b1, r0, r1);
+  }
+  static HP_D void miller_mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0,
+                                    H6& r1) {
+    mul6x2_12(a0, b0, a1, c1, c2, r0, r1);
   }
   static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
                                 H6& C0, Fp& c11, Fp& c12) {

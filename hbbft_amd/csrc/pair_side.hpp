@@ -157,11 +157,11 @@ HP_D HLine side_raw(const PairSide& s, ST& st, int step, const PK& pk) {
   if constexpr (!WALK) {
     return line_load(s.lines + line_at(st.q * PAIR_STEPS + step));
   } else if constexpr (DBL) {
-    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HP_L { return G::dbl_step(T); });
+    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HS_LAMBDA { return G::dbl_step(T); });
   } else {
     Fp xQ, yQ;
     side_q(s, st, xQ, yQ);
-    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HP_L { return G::add_step(T, xQ, yQ); });
+    return pk.template walk<SIDE>(st, [&](typename G::Walk& T) HS_LAMBDA { return G::add_step(T, xQ, yQ); });
   }
 }
 
@@ -250,9 +250,9 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
     if (b != 62) f = h12_sqr<G>(f);
     {
       HLine la, lb;
-      G::template lines_at_p<G1, G2, WF>([&]() HP_L { return side_raw<G, W1, true, 0>(a.s1, A, step, pk); },
-                                         [&]() HP_L { return side_raw<G, W2, true, 1>(a.s2, B, step, pk); }, A, B, neg2,
-                                         la, lb, pk);
+      G::template lines_at_p<G1, G2, WF>([&]() HS_LAMBDA { return side_raw<G, W1, true, 0>(a.s1, A, step, pk); },
+                                         [&]() HS_LAMBDA { return side_raw<G, W2, true, 1>(a.s2, B, step, pk); }, A, B,
+                                         neg2, la, lb, pk);
       // b == 62: f is still 1, and a width may take the line product as f
       constexpr bool FL = G::template first_line<W1, W2>();
       f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4, FL && b == 62);
@@ -260,9 +260,9 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
     step++;
     if ((hb::X_ABS >> b) & 1) {
       HLine la, lb;
-      G::template lines_at_p<G1, G2, WF>([&]() HP_L { return side_raw<G, W1, false, 0>(a.s1, A, step, pk); },
-                                         [&]() HP_L { return side_raw<G, W2, false, 1>(a.s2, B, step, pk); }, A, B, neg2,
-                                         la, lb, pk);
+      G::template lines_at_p<G1, G2, WF>([&]() HS_LAMBDA { return side_raw<G, W1, false, 0>(a.s1, A, step, pk); },
+                                         [&]() HS_LAMBDA { return side_raw<G, W2, false, 1>(a.s2, B, step, pk); }, A, B,
+                                         neg2, la, lb, pk);
       f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
       step++;
     }

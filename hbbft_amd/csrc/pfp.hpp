@@ -35,7 +35,6 @@
 #endif
 
 #define HP_D __device__ __forceinline__
-#define HP_L __attribute__((always_inline))  // on a lambda
 
 namespace hbs {
 
@@ -474,6 +473,8 @@ HP_D H6 h6_mul_12(const H6& x, const Fp& b1, const Fp& b2) {
 //   G::mul6x2_12(a0, b0, a1, c1, c2, r0, r1)  the same with b1 = (0, c1, c2)
 //   G::mul6(a, b)                             one Fp6 product
 //   G::line_product(a0 .. b4, C0, c11, c12)   the product (C0, (0, c11, c12)) of two sparse lines
+//   G::miller_mul6x2 / miller_mul6x2_12 / miller_mul6   the same three products as the Miller loop
+//                                             takes them: times G::MILLER_SCALE, a factor in Fp
 // An operand of a dual product may be a callable that returns it (h6_of): a width that runs the two
 // products one after the other forms the second one's operands after the first product, so that
 // they are not live across its calls.
@@ -490,18 +491,16 @@ HP_D H12 h12_mul(const H12& a, const H12& b) {
   return h12_kcomb(t0, t1, s);
 }
 // complex squaring: t = a0 a1, s = (a0 + a1)(a0 + v a1); c0 = s - t - v t, c1 = 2 t (one pass each)
-// Miller loop only: the value is G::MILLER_SCALE times the square.  A width with a scale other than
-// 1 has the scaled products mul6x2_s, mul6x2_12_s and mul6_s beside the exact ones; every formula
-// here and in h12_mul_lines is linear in its Fp6 products, so the factor carries through.
+// Miller loop only: it takes the width's Miller-loop products (miller_mul6x2 here, miller_mul6x2_12
+// and miller_mul6 in h12_mul_lines), which come out times G::MILLER_SCALE, so the value is that
+// factor times the square; every formula here and in h12_mul_lines is linear in its Fp6 products,
+// so the factor carries through.
 template <class G>
 HP_D H12 h12_sqr(const H12& a) {
   H6 t, s;
-  const auto a1 = [&]() HP_L { return h6_add(a.c0, a.c1); };
-  const auto b1 = [&]() HP_L { return h6_red(h6_add(a.c0, h6_mul_v(a.c1))); };
-  if constexpr (G::MILLER_SCALE == 1)
-    G::mul6x2(a.c0, a.c1, a1, b1, t, s);
-  else
-    G::mul6x2_s(a.c0, a.c1, a1, b1, t, s);
+  const auto a1 = [&]() HS_LAMBDA { return h6_add(a.c0, a.c1); };
+  const auto b1 = [&]() HS_LAMBDA { return h6_red(h6_add(a.c0, h6_mul_v(a.c1))); };
+  G::miller_mul6x2(a.c0, a.c1, a1, b1, t, s);
   return {{fp_red_l(h_add_xi_l(fp_subl(s.c0, t.c0), fp_subl(fp_zero(), t.c2))), fp_red_l(fp_sub2l(s.c1, t.c1, t.c0)),
            fp_red_l(fp_sub2l(s.c2, t.c2, t.c1))},
           {fp_red_l(fp_addl(t.c0, t.c0)), fp_red_l(fp_addl(t.c1, t.c1)), fp_red_l(fp_addl(t.c2, t.c2))}};
@@ -519,15 +518,9 @@ HP_D H12 h12_mul_lines(const H12& f, const Fp& a0, const Fp& a1, const Fp& a4, c
   Fp c11, c12;
   G::line_product(a0, a1, a4, b0, b1, b4, C0, c11, c12);
   if (first) return {C0, {h_zero(), c11, c12}};
-  if constexpr (G::MILLER_SCALE == 1) {
-    G::mul6x2_12(f.c0, C0, f.c1, c11, c12, t0, t1);
-    const H6 s = G::mul6(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
-    return h12_kcomb(t0, t1, s);
-  } else {
-    G::mul6x2_12_s(f.c0, C0, f.c1, c11, c12, t0, t1);
-    const H6 s = G::mul6_s(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
-    return h12_kcomb(t0, t1, s);
-  }
+  G::miller_mul6x2_12(f.c0, C0, f.c1, c11, c12, t0, t1);
+  const H6 s = G::miller_mul6(h6_add(f.c0, f.c1), {C0.c0, fp_add(C0.c1, c11), fp_add(C0.c2, c12)});
+  return h12_kcomb(t0, t1, s);
 }
 template <class G>
 HP_D H12 h12_inv(const H12& a) {
@@ -851,24 +844,6 @@ struct PairPark {
   }
 };
 
-// A/B switches of the lane-pair Miller loop (profiles/r18): HP_PARK = the PairPark above, else
-// NoPark; HP_WALK_FIRST = a TABLE / WALK check walks its WALK side before it fetches the table's line
-#ifndef HP_PARK
-#define HP_PARK 1
-#endif
-#ifndef HP_WALK_FIRST
-#define HP_WALK_FIRST 1
-#endif
-// (profiles/r19): HP_TOOM = the Miller loop's full Fp6 products are h6_mul6 and f carries powers of
-// 6, else Karatsuba and no factor; HP_FIRST_LINE = the first step's line product is taken as f
-// instead of being multiplied into f = 1: 1 = in the checks with a WALK side, 2 = in all of them
-#ifndef HP_TOOM
-#define HP_TOOM 1
-#endif
-#ifndef HP_FIRST_LINE
-#define HP_FIRST_LINE 1
-#endif
-
 // ---------------------------------------------------------------- the lane pair as a width policy
 // What the shared Fp12 operations above and the kernel body and final exponentiation of
 // pair_side.hpp ask of a width.  The lane pair runs every product on its own, one after the other.
@@ -894,21 +869,23 @@ struct LanePair {
   // that the final exponentiation removes: 6 with the five-product h6_mul6, and the sparse product
   // brought to the same factor in its carry passes.  h12_mul, h12_inv and the whole final
   // exponentiation keep the exact products above: a cyclotomic element must not be scaled.
-  static constexpr int MILLER_SCALE = HP_TOOM ? 6 : 1;
-  // the first step's line product is taken as f (17 products less) in the checks that walk a side;
-  // a TABLE / TABLE check was slower with it (profiles/r19)
-  template <bool W1, bool W2>
-  static constexpr bool first_line() { return HP_FIRST_LINE == 2 || (HP_FIRST_LINE == 1 && (W1 || W2)); }
-  static HP_D H6 mul6_s(const H6& a, const H6& b) { return h6_mul6(a, b); }
+  // (Measured against Karatsuba products with no factor in profiles/r19.)
+  static constexpr int MILLER_SCALE = 6;
+  static HP_D H6 miller_mul6(const H6& a, const H6& b) { return h6_mul6(a, b); }
   template <class A1, class B1>
-  static HP_D void mul6x2_s(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+  static HP_D void miller_mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
     r0 = h6_mul6(a0, b0);
     r1 = h6_mul6(h6_of(a1), h6_of(b1));
   }
-  static HP_D void mul6x2_12_s(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
+  static HP_D void miller_mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0,
+                                    H6& r1) {
     r0 = h6_mul6(a0, b0);
-    r1 = h6_mul_12<6>(a1, c1, c2);
+    r1 = h6_mul_12<MILLER_SCALE>(a1, c1, c2);
   }
+  // the first step's line product is taken as f (17 products less) in the checks that walk a side;
+  // a TABLE / TABLE check was slower with it (profiles/r19)
+  template <bool W1, bool W2>
+  static constexpr bool first_line() { return W1 || W2; }
   // each coefficient is reduced (one carry pass) as soon as its products exist
   static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
                                 H6& C0, Fp& c11, Fp& c12) {
@@ -924,13 +901,8 @@ struct LanePair {
   static HP_D H12 frob1(const H12& f) { return h12_frob1(f); }
   static HP_D H12 frob2(const H12& f) { return h12_frob2(f); }
 
-#if HP_PARK
   template <bool W1, bool W2, int GEN>
-  using Park = PairPark<W1, W2, GEN>;
-#else
-  template <bool W1, bool W2, int GEN>
-  using Park = NoPark;
-#endif
+  using Park = PairPark<W1, W2, GEN>;  // against NoPark: profiles/r18
 
   // a side's line (c0, c1, c4) evaluated at its P: (c0, c1 xP, c4 yP), or 1 for an inactive pair.
   // P comes from the parking hook (the side's registers, or the stash), each coordinate as its
@@ -952,7 +924,7 @@ struct LanePair {
   template <bool G1, bool G2, bool WALK_FIRST, class RA, class RB, class ST, class PK>
   static HP_D void lines_at_p(const RA& raw_a, const RB& raw_b, const ST& A, const ST& B, bool neg2, HLine& la,
                               HLine& lb, const PK& pk) {
-    if constexpr (WALK_FIRST && HP_WALK_FIRST) {
+    if constexpr (WALK_FIRST) {
       lb = line_at_p<G2, 1>(raw_b(), B, neg2, pk);
       la = line_at_p<G1, 0>(raw_a(), A, false, pk);
     } else {

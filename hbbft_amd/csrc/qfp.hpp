@@ -14,7 +14,8 @@
 //                and t1 -- the sums and reductions inside are split too, not repeated;
 //   h6_mul_q     one Fp6 product as three dual Fp2 rounds (Karatsuba's third product);
 //   h_mul2 / h_sqr2 / fp_mul2   single dual products (line products, doubling step, cyclotomic
-//                squaring's nine squares in five rounds, line evaluation at P).
+//                squaring's nine squares in five rounds, line evaluation at P); h_mul2 / h_sqr2 are
+//                also the rounds of the lane-quad G2 group law (g2quad.hpp).
 // A check's per-lane product count falls to ~0.55 of the lane pair's, so a batch of 16,384 checks
 // (1,024 waves: one per SIMD) finishes in a little over half the lane-pair kernel's latency floor.
 // Formulas and value contracts are pfp.hpp's (pairing 0.14's, restated in oracle/c/bls_cpu.c).
@@ -189,7 +190,6 @@ struct LaneQuad {
   static HP_D HLine dbl_step(HJac& T) { return h_dbl_step_q(T); }
   static HP_D HLine add_step(HJac& T, const Fp& xQ, const Fp& yQ) { return h_add_step_q(T, xQ, yQ); }
 
-  static constexpr int MILLER_SCALE = 1;  // exact Karatsuba products in the Miller loop too
   template <bool W1, bool W2>
   static constexpr bool first_line() { return false; }
   static HP_D H6 mul6(const H6& a, const H6& b) { return h6_mul_q(a, b); }
@@ -199,6 +199,16 @@ struct LaneQuad {
   }
   static HP_D void mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0, H6& r1) {
     h6_mul2(a0, b0, a1, {h_zero(), c1, c2}, r0, r1);
+  }
+  static constexpr int MILLER_SCALE = 1;  // the Miller loop takes the exact Karatsuba products too
+  static HP_D H6 miller_mul6(const H6& a, const H6& b) { return mul6(a, b); }
+  template <class A1, class B1>
+  static HP_D void miller_mul6x2(const H6& a0, const H6& b0, const A1& a1, const B1& b1, H6& r0, H6& r1) {
+    mul6x2(a0, b0, a1, b1, r0, r1);
+  }
+  static HP_D void miller_mul6x2_12(const H6& a0, const H6& b0, const H6& a1, const Fp& c1, const Fp& c2, H6& r0,
+                                    H6& r1) {
+    mul6x2_12(a0, b0, a1, c1, c2, r0, r1);
   }
   static HP_D void line_product(const Fp& a0, const Fp& a1, const Fp& a4, const Fp& b0, const Fp& b1, const Fp& b4,
                                 H6& C0, Fp& c11, Fp& c12) {

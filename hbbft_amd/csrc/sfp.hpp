@@ -1,5 +1,5 @@
-// Signed-limb BLS12-381 Fp / Fp2 (namespace hbs): the base of the lane-pair tower (pfp.hpp) and of the
-// lane-quad G1 kernels (k_g1quad.hip).
+// Signed-limb BLS12-381 Fp (namespace hbs): the base of the lane-pair tower (pfp.hpp) and of the
+// lane-quad G1 kernels (k_g1quad.hip).  Fp2 exists only split over a lane pair (pfp.hpp).
 //
 // Representation: 14 int32 limbs of radix 2^28, value = sum l[i] 2^(28 i) (signed), Montgomery
 // form with R = 2^392.  "Normalised": l[0..12] in [0, 2^28), l[13] signed.
@@ -24,6 +24,7 @@
 #else
 #define HS_HD inline
 #endif
+#define HS_LAMBDA __attribute__((always_inline))  // on a lambda
 
 // Product linkage: inlined by default; a translation unit may define HS_MULFN as a static
 // non-inlined device function to keep one copy of the product hot in the instruction cache (the
@@ -45,9 +46,6 @@ constexpr int32_t NEGP_L[NL] = {21845,     1048576,  201326662, 5354,      16540
 
 struct Fp {
   int32_t l[NL];
-};
-struct Fp2 {
-  Fp c0, c1;
 };
 
 // Montgomery digit m = low 28 bits of (column * -p^-1).  (v_mul_lo_u32 issues at full rate on gfx950,
@@ -260,36 +258,19 @@ HS_HD Fp fp_inv(const Fp& a) {  // a^(p-2)
   return r;
 }
 
-// ------------------------------------------------------------------ Fp2 = Fp[u]/(u^2+1)
-// contracts: f2_mul / f2_sqr inputs |.| < 8p (normalised) -> outputs |.| < 2.5p
-HS_HD Fp2 f2_zero() { return {fp_zero(), fp_zero()}; }
-HS_HD Fp2 f2_one() { return {fp_one(), fp_zero()}; }
-HS_HD Fp2 f2_add(const Fp2& a, const Fp2& b) { return {fp_add(a.c0, b.c0), fp_add(a.c1, b.c1)}; }
-HS_HD Fp2 f2_sub(const Fp2& a, const Fp2& b) { return {fp_sub(a.c0, b.c0), fp_sub(a.c1, b.c1)}; }
-HS_HD Fp2 f2_neg(const Fp2& a) { return {fp_neg(a.c0), fp_neg(a.c1)}; }
-HS_HD Fp2 f2_conj(const Fp2& a) { return {a.c0, fp_neg(a.c1)}; }
-HS_HD Fp2 f2_lin(int k1, const Fp2& a, int k2, const Fp2& b) { return {fp_lin(k1, a.c0, k2, b.c0), fp_lin(k1, a.c1, k2, b.c1)}; }
-HS_HD Fp2 f2_sel(bool c, const Fp2& a, const Fp2& b) { return {fp_sel(c, a.c0, b.c0), fp_sel(c, a.c1, b.c1)}; }
-HS_HD Fp2 f2_red(const Fp2& a) { return {fp_reduce(a.c0), fp_reduce(a.c1)}; }
-HS_HD Fp2 f2_mul_xi(const Fp2& a) { return {fp_sub(a.c0, a.c1), fp_add(a.c0, a.c1)}; }  // * (1 + u)
-HS_HD Fp2 f2_mul(const Fp2& a, const Fp2& b) {
-  const Fp t0 = fp_mul(a.c0, b.c0);
-  const Fp t1 = fp_mul(a.c1, b.c1);
-  const Fp t2 = fp_mul(fp_addl(a.c0, a.c1), fp_addl(b.c0, b.c1));
-  Fp c1 = fp_subl(fp_subl(t2, t0), t1);
-  fp_norm(c1);
-  return {fp_sub(t0, t1), c1};
+// The double-and-add of every lane-split group law (g1quad.hpp, g2quad.hpp): for the bits top .. 0
+// of k, acc = dbl(acc), then acc = add(acc) where the bit is set.  The caller gives the starting
+// accumulator (the point itself, for the bits below k's leading one) and the addition of its point.
+// Not unrolled: the loop control is uniform and one copy of the group law stays in the I-cache.
+template <class P, class K, class DBL, class ADD>
+HS_HD P dbl_and_add(const P& start, K k, int top, const DBL& dbl, const ADD& add) {
+  P acc = start;
+#pragma unroll 1
+  for (int i = top; i >= 0; i--) {
+    acc = dbl(acc);
+    if ((k >> i) & 1) acc = add(acc);
+  }
+  return acc;
 }
-HS_HD Fp2 f2_sqr(const Fp2& a) {
-  const Fp s = fp_mul(fp_addl(a.c0, a.c1), fp_subl(a.c0, a.c1));
-  const Fp m = fp_mul(a.c0, a.c1);
-  return {s, fp_add(m, m)};
-}
-HS_HD Fp2 f2_mul_fp(const Fp2& a, const Fp& s) { return {fp_mul(a.c0, s), fp_mul(a.c1, s)}; }
-HS_HD Fp2 f2_inv(const Fp2& a) {
-  const Fp t = fp_inv(fp_reduce(fp_add(fp_sqr(a.c0), fp_sqr(a.c1))));
-  return {fp_mul(a.c0, t), fp_neg(fp_mul(a.c1, t))};
-}
-HS_HD bool f2_is_zero(const Fp2& a) { return fp_is_zero(a.c0) && fp_is_zero(a.c1); }
 
 }  // namespace hbs

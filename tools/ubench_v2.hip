@@ -121,6 +121,15 @@ __global__ void __launch_bounds__(256) k_fpmul(uint32_t* out, const uint32_t* in
 // Inputs normalised (limbs 0..12 in [0, 2^28)); b is read from this lane's LDS slot (the AMDGPU
 // calling convention passes only 32 VGPR arguments).
 struct Fp2r { Fp c0, c1; };
+// the baseline: Karatsuba over three separate Montgomery products, both components on one lane
+HS_HD Fp2r f2_mul(const Fp2r& a, const Fp2r& b) {
+  const Fp t0 = fp_mul(a.c0, b.c0);
+  const Fp t1 = fp_mul(a.c1, b.c1);
+  const Fp t2 = fp_mul(fp_addl(a.c0, a.c1), fp_addl(b.c0, b.c1));
+  Fp c1 = fp_subl(fp_subl(t2, t0), t1);
+  fp_norm(c1);
+  return {fp_sub(t0, t1), c1};
+}
 HS_MULFN Fp2r f2_mul_lazy(HS_P14(x), HS_P14(z), const int4* __restrict__ slot) {
   const Fp a0 = {{HS_L14(x)}};
   const Fp a1 = {{HS_L14(z)}};
@@ -179,7 +188,7 @@ HS_MULFN Fp2r f2_mul_lazy(HS_P14(x), HS_P14(z), const int4* __restrict__ slot) {
 template <int V>
 __global__ void __launch_bounds__(256) k_f2mul(uint32_t* out, const uint32_t* in, int iters) {
   extern __shared__ int4 slds[];
-  Fp2 a, b;
+  Fp2r a, b;
 #pragma unroll
   for (int j = 0; j < NL; j++) {
     a.c0.l[j] = (int32_t)in[j * 64 + (threadIdx.x & 63)];
