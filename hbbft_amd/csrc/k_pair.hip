@@ -36,9 +36,9 @@ namespace hbs {
 // and nothing else.  The parked powers are then decompressed with ONE Fp2 inversion (Montgomery's
 // simultaneous inversion of the denominators 4 a1: prefix products, h_inv_vartime,
 // back-substitution).  The four set bits from 57 up are close together: t = f^(2^57) is raised to
-// |x| >> 57 = 105 with six Granger-Scott squarings and three products (h_exp_high), which costs less
-// than decompressing three more powers (measured: EXP_TOP = 57 against 60 and 63,
-// profiles/r10/README.md).  f^|x| = t^105 f^(2^48) f^(2^16).
+// |x| >> 57 = 105 = 7 x 15 with seven Granger-Scott squarings and two products (h_exp_high), which
+// costs less than decompressing three more powers (measured with six squarings and three products:
+// EXP_TOP = 57 against 60 and 63, profiles/r10/README.md).  f^|x| = t^105 f^(2^48) f^(2^16).
 //
 // The compressed form needs every parked a1 != 0.  The product of the denominators tells (one zero
 // test); then the exponentiation runs the Granger-Scott square-and-multiply loop instead (h_exp_gs).
@@ -81,8 +81,30 @@ static __device__ __noinline__ void h_exp_gs(const ExpPark& pk, bool plus1, H12&
   out = r;
 }
 
-// t^EXP_HIGH, square-and-multiply from the top with Granger-Scott squarings
+// t^EXP_HIGH with Granger-Scott squarings.  A/B switch (profiles/r21): 1 = 105 = 7 x 15 with the
+// inverses as conjugates, u = t^8 conj(t) and u^16 conj(u): seven squarings and two products; 0 =
+// square-and-multiply from the top, six and three.
+#ifndef HP_EXP715
+#define HP_EXP715 1
+#endif
 HP_D H12 h_exp_high(const H12& t) {
+#if HP_EXP715
+  static_assert(EXP_HIGH == 105 && EXP_HIGH_BITS == 7, "the chain is 105 = (8 - 1)(16 - 1)");
+  // both passes through one copy of the square and of the product: r <- r^(2^(3 + pass)) / b, b <- r.
+  // Bounds: b is reduced (|.| < 2p, normalised) -- t, hc_decompress's output, in pass 0 and an h12_mul
+  // output in pass 1 -- so h12_conj(b)'s fp_neg (0 - x, one carry pass) is normalised with |.| < 2p,
+  // and r is an h12_cyclo_sqr output, reduced: both are h12_mul's "inputs reduced", whose sums of two
+  // components stay normalised and < 4p, h6_mul's input bound.
+  H12 r = t, b = t;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+#pragma unroll 1
+    for (int k = 0; k < 3 + pass; k++) r = h12_cyclo_sqr(r);
+    r = h12_mul<LanePair>(r, h12_conj(b));
+    b = r;
+  }
+  return r;
+#else
   H12 r = t;
 #pragma unroll 1
   for (int k = EXP_HIGH_BITS - 2; k >= 0; k--) {
@@ -90,6 +112,7 @@ HP_D H12 h_exp_high(const H12& t) {
     if ((EXP_HIGH >> k) & 1) r = h12_mul<LanePair>(r, t);
   }
   return r;
+#endif
 }
 
 // decompress the parked powers with one shared inversion, raise the highest to EXP_HIGH and
