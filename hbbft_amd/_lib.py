@@ -33,6 +33,8 @@ SIGNATURES = [
     ("hbh_verify_dec_shares_grouped", _I, [_P, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_dbg_group_sums", _I, [_P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_engine_set_group_sum_impl", _I, [_P, _I]),
+    ("hbh_engine_set_group_scalar_form", _I, [_P, _I]),
+    ("hbh_dbg_group_sums_form", _I, [_P, _I, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
     ("hbh_verify_pairing_eq_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _SZ, _P, _P]),
     ("hbh_dbg_pairing", _I, [_P, _SZ, _P, _P, _P]),
     ("hbh_interpolate_g2", _I, [_P, _SZ, _I, _P, _P, _P, _P]),
@@ -125,6 +127,8 @@ HASH_ROUNDS = 32  # HBH_HASH_ROUNDS
 AUTO_HASH_DEVICE_MIN = 4096  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r14)
 GSUM_AUTO, GSUM_CHAIN, GSUM_BUCKET = 0, 1, 2  # HBH_GSUM_*
 AUTO_GSUM_G1_BUCKET_MIN, AUTO_GSUM_G2_BUCKET_MIN = 0, 0  # HBH_AUTO_GSUM_G*_BUCKET_MIN (0: never; profiles/r17)
+GSCALAR_INT128, GSCALAR_DIGITS = 0, 1  # HBH_GSCALAR_*: how a grouped call reads and draws its scalars
+GFORM_INT128, GFORM_X4, GFORM_X2 = 0, 1, 2  # HBH_GFORM_* (hbh_dbg_group_sums_form)
 GROUP_TILE = 128  # csrc/group_plan.hpp GROUP_TILE: items per tile of the grouped share checks' sums
 
 

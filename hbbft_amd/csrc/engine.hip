@@ -120,6 +120,7 @@ struct hbh_engine {
   int ack_impl = HBH_ACK_AUTO;  // Ack-check kernel of commitment sets (hbh_engine_set_ack_impl)
   int dec_impl = HBH_DEC_AUTO;  // point-decoding kernels (hbh_engine_set_decode_impl)
   int gsum_impl = HBH_GSUM_AUTO;  // group sums of the grouped share checks (hbh_engine_set_group_sum_impl)
+  int gscalar_form = HBH_GSCALAR_INT128;  // how the grouped share checks read and draw scalars (hbh_engine_set_group_scalar_form)
   int hash_impl = HBH_HASH_AUTO;  // where the curve half of hash_g2 runs (hbh_engine_set_hash_impl)
   int hash_rounds = HBH_HASH_ROUNDS;  // sampler rounds of the device form (hbh_dbg_set_hash_rounds)
   StageTimer timer;
@@ -702,6 +703,14 @@ int hbh_engine_set_group_sum_impl(hbh_engine* e, int impl) {
     return fail(HBH_ERR_ARG, "unknown group-sum implementation");
   std::lock_guard<std::mutex> lk(e->mu);
   e->gsum_impl = impl;
+  return HBH_OK;
+}
+
+int hbh_engine_set_group_scalar_form(hbh_engine* e, int form) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (form != HBH_GSCALAR_INT128 && form != HBH_GSCALAR_DIGITS) return fail(HBH_ERR_ARG, "unknown group scalar form");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->gscalar_form = form;
   return HBH_OK;
 }
 
@@ -2126,15 +2135,19 @@ int hbh_verify_pairing_eq_set_dev(hbh_engine* e, void* stream, size_t n, const v
 // ---------------------------------------------------------------- grouped random-combination share checks
 // Opt-in forms of hbh_verify_sig_shares / hbh_verify_dec_shares (include/hbbft_hip.h): the items that
 // share a table entry are settled by ONE pairing check on their random linear combination
-// (group_plan.hpp plans the groups, k_rlc.hip sums them); the items of a group whose check fails, and
+// (group_plan.hpp plans the groups, k_rlc.hip sums them, k_rlc_digits.hip under the digit forms of the
+// scalars); the items of a group whose check fails, and
 // the items alone in their group, take the per-share check, so every reported 0 is exact.
 #include <sys/random.h>
 
+#include "group_digits.hpp"
 #include "group_plan.hpp"
 
 namespace {
 
-constexpr size_t RLC_BYTES = 16;  // one scalar: 128 bits, little-endian
+constexpr size_t RLC_BYTES = 16;  // one scalar: 128 bits, a little-endian integer or the form's LE digits
+static_assert(HBH_GFORM_INT128 == gd::FORM_INT128 && HBH_GFORM_X4 == gd::FORM_X4 && HBH_GFORM_X2 == gd::FORM_X2,
+              "the ABI's forms are group_digits.hpp's");
 
 bool rlc_is_zero(const uint8_t* r) {
   uint8_t o = 0;
@@ -2153,7 +2166,7 @@ int os_random(uint8_t* out, size_t bytes) {
 }
 
 // The n scalars of a call: the caller's (none may be zero), or n x 128 bits from the OS with a zero
-// draw replaced.
+// draw replaced.  The same in every form: the all-zero bytes are the zero integer and the all-zero tuple.
 int rlc_scalars(size_t n, const uint8_t* given, std::vector<uint8_t>& r) {
   r.resize(n * RLC_BYTES);
   if (given) {
@@ -2200,10 +2213,17 @@ int upload_plan(hbh_engine* e, hipStream_t s, const GroupPlan& P, const std::vec
 }
 
 // out[c] = sum of r_i P_i over combined group c, for the n points d_pts (G1 or G2 ABI words); tile sums
-// in `region` (0 / 1) of e->work, which the caller sized for two G2 regions
+// in `region` (0 / 1) of e->work, which the caller sized for two G2 regions.  form: HBH_GFORM_* of the
+// scalars; the digit forms always run k_rlc_digits.hip, hbh_engine_set_group_sum_impl governs INT128 only.
 int launch_group_sums(hbh_engine* e, hipStream_t s, bool g2, size_t n, const void* d_pts, const GroupDev& d, int region,
-                      void* d_out) {
+                      void* d_out, int form) {
   void* tiles = (uint8_t*)e->work.p + (size_t)region * d.ntile * hbl::group_tile_bytes(true);
+  if (form != HBH_GFORM_INT128) {
+    HBH_CHECK((g2 ? hbl::group_digits_g2 : hbl::group_digits_g1)(s, form, d.ntile, (int)n, d.max_len, d_pts, d.scalars,
+                                                                 d.perm, d.tile_off, d.tile_len, tiles));
+    HBH_CHECK((g2 ? hbl::group_join_g2 : hbl::group_join_g1)(s, d.ncomb, d.ctile, tiles, d_out));
+    return HBH_OK;
+  }
   // the form of this sum: forced, or AUTO by the items of the call (a threshold of 0: never BUCKET)
   const size_t bucket_min = g2 ? HBH_AUTO_GSUM_G2_BUCKET_MIN : HBH_AUTO_GSUM_G1_BUCKET_MIN;
   const bool bucket =
@@ -2261,8 +2281,10 @@ int run_grouped(hbh_engine* e, size_t n, const uint8_t* a, const uint8_t* b, boo
     HBH_CHECK(e->out_v.ensure(nc));
     {
       StageScope tm(e, s, HBH_STAGE_CURVE);
-      rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p);
-      if (!rc) rc = launch_group_sums(e, s, !dec, n, dec ? e->in_p2.p : e->in_d.p, d, 1, e->in_c.p);
+      // one residue r_i per item on both sides: X4 where a sum is in G2, X2 where both are in G1
+      const int form = e->gscalar_form == HBH_GSCALAR_DIGITS ? (dec ? HBH_GFORM_X2 : HBH_GFORM_X4) : HBH_GFORM_INT128;
+      rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p, form);
+      if (!rc) rc = launch_group_sums(e, s, !dec, n, dec ? e->in_p2.p : e->in_d.p, d, 1, e->in_c.p, form);
       if (rc) return rc;
     }
     // sig: e(sum r pk, H) == e(g1, sum r sig);  dec: e(sum r D, H_uv) == e(sum r pk, W)
@@ -2325,7 +2347,16 @@ int hbh_verify_dec_shares_grouped(hbh_engine* e, size_t n, const uint8_t* shares
 
 int hbh_dbg_group_sums(hbh_engine* e, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts, size_t ngroups,
                        const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1, uint8_t* out_g2) {
+  return hbh_dbg_group_sums_form(e, HBH_GFORM_INT128, n, g1_pts, g2_pts, ngroups, group_idx, scalars, out_g1, out_g2);
+}
+
+int hbh_dbg_group_sums_form(hbh_engine* e, int form, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts,
+                            size_t ngroups, const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1,
+                            uint8_t* out_g2) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (form != HBH_GFORM_INT128 && form != HBH_GFORM_X4 && form != HBH_GFORM_X2)
+    return fail(HBH_ERR_ARG, "unknown group scalar form");
+  if (form == HBH_GFORM_X2 && g2_pts) return fail(HBH_ERR_ARG, "the X2 form has no G2 sum");
   if ((g1_pts && !out_g1) || (g2_pts && !out_g2)) return fail(HBH_ERR_ARG, "null pointer");
   if (g1_pts) std::memset(out_g1, 0, ngroups * HBH_G1_BYTES);  // an absent entry sums to O
   if (g2_pts) std::memset(out_g2, 0, ngroups * HBH_G2_BYTES);
@@ -2348,14 +2379,14 @@ int hbh_dbg_group_sums(hbh_engine* e, size_t n, const uint8_t* g1_pts, const uin
   if (g1_pts) {
     HBH_CHECK(upload(s, e->in_p1, g1_pts, n * HBH_G1_BYTES));
     HBH_CHECK(e->out_x.ensure(nc * HBH_G1_BYTES));
-    rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p);
+    rc = launch_group_sums(e, s, false, n, e->in_p1.p, d, 0, e->out_x.p, form);
     if (rc) return rc;
     HBH_CHECK(download(s, s1.data(), e->out_x, s1.size()));
   }
   if (g2_pts) {
     HBH_CHECK(upload(s, e->in_d, g2_pts, n * HBH_G2_BYTES));
     HBH_CHECK(e->in_c.ensure(nc * HBH_G2_BYTES));
-    rc = launch_group_sums(e, s, true, n, e->in_d.p, d, 1, e->in_c.p);
+    rc = launch_group_sums(e, s, true, n, e->in_d.p, d, 1, e->in_c.p, form);
     if (rc) return rc;
     HBH_CHECK(download(s, s2.data(), e->in_c, s2.size()));
   }

@@ -1,5 +1,5 @@
 // Host-side launchers of the HIP kernels.  Each kernel family lives in its own translation unit
-// (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip, k_rlc.hip) so the Makefile
+// (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip, k_rlc.hip, k_rlc_digits.hip) so the Makefile
 // compiles them in parallel; engine.hip owns the C ABI, device buffers and streams and calls only
 // these functions.  Its host arithmetic and planning live in host_fr.hpp, wire_host.hpp and ack_plan.hpp.
 #pragma once
@@ -173,6 +173,16 @@ hipError_t group_bucket_g1(hipStream_t s, int ntile, int n, int max_len, const v
                            const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
 hipError_t group_bucket_g2(hipStream_t s, int ntile, int n, int max_len, const void* pts, const uint32_t* scalars,
                            const uint32_t* perm, const uint32_t* tile_off, const uint32_t* tile_len, void* tile_sums);
+// group_digits_g*: the tile sums of group_sum_g* for scalars in a digit form (k_rlc_digits.hip; form =
+// gd::FORM_X4 or gd::FORM_X2 of group_digits.hpp, X4 only for G2): an item's 4 words are short digits in the
+// endomorphism basis and run as joint double-and-add chains of 32 (G2), 96 (G1, X4) or 64 (G1, X2) steps.
+// Same arguments otherwise, same tile records, so group_join_g* serves them too.
+hipError_t group_digits_g1(hipStream_t s, int form, int ntile, int n, int max_len, const void* pts,
+                           const uint32_t* scalars, const uint32_t* perm, const uint32_t* tile_off,
+                           const uint32_t* tile_len, void* tile_sums);
+hipError_t group_digits_g2(hipStream_t s, int form, int ntile, int n, int max_len, const void* pts,
+                           const uint32_t* scalars, const uint32_t* perm, const uint32_t* tile_off,
+                           const uint32_t* tile_len, void* tile_sums);
 hipError_t group_join_g1(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 hipError_t group_join_g2(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 

@@ -63,6 +63,19 @@ def _join(points, size):
 # hbh_grouped_stats of one grouped share check (Engine.verify_*_shares_grouped)
 GroupedStats = collections.namedtuple("GroupedStats", "groups groups_passed singles fallback_items")
 
+X_ABS = 0xd201000000010000  # |x|, the curve parameter
+
+
+def digit_scalar(form, digits):
+    """A grouped call's scalar in a digit form as (packed, value): ``packed`` is the int whose 16
+    little-endian bytes hold the digits (what the scalars arguments take), ``value`` the residue r_i
+    they stand for.  GFORM_X4: four digits < 2^32, value = sum a_j |x|^j; GFORM_X2: two digits < 2^64,
+    value = b0 + b1 |x|^2."""
+    bits, base = {_lib.GFORM_X4: (32, X_ABS), _lib.GFORM_X2: (64, X_ABS * X_ABS)}[form]
+    if len(digits) != 128 // bits or not all(0 <= d < 1 << bits for d in digits):
+        raise ValueError("digits out of range for the form")
+    return (sum(d << (bits * j) for j, d in enumerate(digits)), sum(d * base ** j for j, d in enumerate(digits)))
+
 
 class Engine:
     """One engine per GPU (one process per GPU for multi-GPU runs)."""
@@ -235,6 +248,13 @@ class Engine:
         vp = ctypes.c_void_p
         check(self._l.hbh_hash_g2_dev(self._h, vp(stream) if stream else None, n, vp(d_seeds), vp(d_out)))
 
+    def set_group_scalar_form(self, form):
+        """HBH_GSCALAR_*: 0 = the scalars of the grouped share checks are 128-bit integers (default),
+        1 = short digits in the endomorphism basis (X4 for verify_sig_shares_grouped, X2 for
+        verify_dec_shares_grouped; joint chains of 32 / 96 / 64 steps).  Governs how scalars are drawn
+        and how given ones are read; verdicts, stats and the soundness bound are the same."""
+        check(self._l.hbh_engine_set_group_scalar_form(self._h, int(form)))
+
     def set_hash_impl(self, impl):
         """HBH_HASH_*: 0 = auto (default: the device from AUTO_HASH_DEVICE_MIN messages per call), 1 = the
         host stage, 2 = the device.  Governs hash_g2, hash_g1_g2, hash_g1_g2_bp, verify_signed,
@@ -276,7 +296,9 @@ class Engine:
         """verify_sig_shares with one pairing check per document on a random linear combination of
         its shares, and the per-share check for the documents whose check fails
         (hbh_verify_sig_shares_grouped): (verdicts, GroupedStats).  ``scalars`` None: the engine draws
-        them; given scalars (ints in [1, 2^128)) are used as they are -- the caller's responsibility."""
+        them; given scalars (ints in [1, 2^128)) are used as they are -- the caller's responsibility.
+        Under set_group_scalar_form(GSCALAR_DIGITS) the 16 bytes of a scalar are the form's digits
+        (``digit_scalar`` packs them)."""
         pkb, sgb, hb = _join(pks, G1_BYTES), _join(sigs, G2_BYTES), _join(hashes, G2_BYTES)
         n = len(pkb) // G1_BYTES
         if len(sgb) // G2_BYTES != n:
@@ -326,6 +348,28 @@ class Engine:
         vp = ctypes.c_void_p
         check(self._l.hbh_dbg_group_sums(self._h, n, k1[1], k2[1], ngroups, pgi, pr, ctypes.cast(o1, vp),
                                          ctypes.cast(o2, vp)))
+        r1, r2 = bytes(o1), bytes(o2)
+        return (None if b1 is None else [r1[k * G1_BYTES:(k + 1) * G1_BYTES] for k in range(ngroups)],
+                None if b2 is None else [r2[k * G2_BYTES:(k + 1) * G2_BYTES] for k in range(ngroups)])
+
+    def dbg_group_sums_form(self, form, g1_pts, g2_pts, ngroups, group_idx, scalars):
+        """dbg_group_sums with the scalars read in ``form`` (hbh_dbg_group_sums_form): GFORM_INT128,
+        GFORM_X4 (four LE u32 digits in base |x|) or GFORM_X2 (two LE u64 digits in base |x|^2, G1
+        only).  Scalars: packed bytes, or ints holding the 16 bytes little-endian (``digit_scalar``).
+        Tests only."""
+        b1 = None if g1_pts is None else _join(g1_pts, G1_BYTES)
+        b2 = None if g2_pts is None else _join(g2_pts, G2_BYTES)
+        n = len(group_idx)
+        if (b1 is not None and len(b1) != n * G1_BYTES) or (b2 is not None and len(b2) != n * G2_BYTES):
+            raise ValueError("points / group_idx length mismatch")
+        gi, pgi = _u32(group_idx, n)
+        rk, pr = self._rlc_scalars(scalars, n)
+        k1, k2 = buf(b1 or None), buf(b2 or None)
+        o1 = (ctypes.c_uint8 * max(ngroups * G1_BYTES, 1))()
+        o2 = (ctypes.c_uint8 * max(ngroups * G2_BYTES, 1))()
+        vp = ctypes.c_void_p
+        check(self._l.hbh_dbg_group_sums_form(self._h, int(form), n, k1[1], k2[1], ngroups, pgi, pr,
+                                              ctypes.cast(o1, vp), ctypes.cast(o2, vp)))
         r1, r2 = bytes(o1), bytes(o2)
         return (None if b1 is None else [r1[k * G1_BYTES:(k + 1) * G1_BYTES] for k in range(ngroups)],
                 None if b2 is None else [r2[k * G2_BYTES:(k + 1) * G2_BYTES] for k in range(ngroups)])

@@ -18,6 +18,7 @@ import concurrent.futures
 import time
 
 from . import hoststage
+from . import _lib
 from ._lib import G1_BYTES, G2_BYTES
 
 
@@ -147,13 +148,26 @@ class BatchVerifier:
     that fail.  A reported invalid share is exact; a valid verdict is the reference's except with
     probability at most 1 / (2^128 - 1) per group, and combine_and_verify_sig still checks the combined
     signature.  Ciphertext checks, the cache and the counters are unchanged.  The grouped calls are
-    stateless, so ``grouped`` with ``g2_capacity`` > 0 is a ValueError.  Default: off."""
+    stateless, so ``grouped`` with ``g2_capacity`` > 0 is a ValueError.  Default: off.
 
-    def __init__(self, engine, combine_engine=None, g2_capacity=0, grouped=False):
+    ``scalar_form`` (with ``grouped`` only; anything else is a ValueError): how the engine draws the
+    scalars of the grouped calls, "int128" (the default: 128-bit integers) or "digits" (short digits in
+    the endomorphism basis, Engine.set_group_scalar_form: shorter chains in the group sums, the same
+    2^128 - 1 non-zero residues and the same bound).  The verifier sets its form on the engine before
+    the grouped calls of each drain."""
+
+    SCALAR_FORMS = {"int128": _lib.GSCALAR_INT128, "digits": _lib.GSCALAR_DIGITS}
+
+    def __init__(self, engine, combine_engine=None, g2_capacity=0, grouped=False, scalar_form=None):
         if grouped and g2_capacity > 0:
             raise ValueError("grouped share checks are stateless: grouped=True takes no g2_capacity")
+        if scalar_form is not None and not grouped:
+            raise ValueError("scalar_form is a choice of the grouped share checks: it needs grouped=True")
+        if scalar_form is not None and scalar_form not in self.SCALAR_FORMS:
+            raise ValueError("scalar_form must be 'int128' or 'digits'")
         self.eng = engine
         self.grouped = bool(grouped)
+        self.scalar_form = (scalar_form or "int128") if grouped else None
         self._g2 = engine.g2_set(g2_capacity) if g2_capacity > 0 else None
         self._g2_slot = {}     # point -> slot
         self._g2_ref = {}      # point -> open keys that use it
@@ -504,6 +518,8 @@ class BatchVerifier:
         fn = {"ct": "verify_ciphertexts", "sig": "verify_sig_shares", "dec": "verify_dec_shares"}
         nargs = {"ct": 3, "sig": 4, "dec": 5}
         if self.grouped:  # no set (the constructor's rule), so every job carries the stateless arguments
+            if any(kind != "ct" for kind, _, _ in jobs):
+                self.eng.set_group_scalar_form(self.SCALAR_FORMS[self.scalar_form])
             return [(kind, keys, getattr(self.eng, fn[kind])(*args) if kind == "ct" else
                      getattr(self.eng, fn[kind] + "_grouped")(*args)[0]) for kind, keys, args in jobs]
         return [(kind, keys, getattr(self.eng, fn[kind])(*args) if len(args) == nargs[kind] else self._run_set(kind, *args))

@@ -204,6 +204,10 @@ GSUM_OPS = {"g1": (G1_DBL[0], G1_MADD[0], G1_ADD[0]), "g2": (G2_DBL[0], G2_MADD[
 GSUM_WINDOWS = {"g1": 64, "g2": 32}      # two-bit windows: 128 bits of r (G1), d0 and d1 < |x| < 2^64 (G2)
 GSUM_TAIL_SEGS = 8                       # csrc/group_bucket.hpp TAIL_SEGS
 GSUM_D2_RATE = 1.0 - (X_ABS * X_ABS) / 2.0 ** 128   # share of the scalars >= |x|^2: the psi^2(P) term
+# The digit forms of the scalars (hbh_engine_set_group_scalar_form, csrc/group_digits.hpp): joint chains of
+# two digits, (chains per item, steps per chain) by (kind, form); a step adds unless both digit bits are 0.
+GSUM_DIGIT_CHAINS = {("g1", "x4"): (1, 96), ("g1", "x2"): (1, 64), ("g2", "x4"): (2, 32)}
+GSUM_DIGIT_ADD_RATE = 0.75
 
 
 def _gsum_tail(kind):
@@ -224,8 +228,17 @@ def group_sum_ops(kind, impl, L):
         addition of the second chain into the first; then L - 1 additions of the tree.
       bucket (k_group_bucket): 3/4 of the (term, window) digits are nonzero, one mixed addition each
         (G1: L terms x 64 windows; G2: 2 L terms x 32 windows, plus the psi^2(P) terms in window 0);
-        3 additions and a doubling per window to reduce the buckets; the tail."""
+        3 additions and a doubling per window to reduce the buckets; the tail.
+      x4 / x2 (k_group_digits, the digit forms): one joint chain per pair of digits, a doubling per step
+        and a mixed addition at 3/4 of the steps (G1: 96 steps under x4, 64 under x2; G2, x4 only: two
+        chains of 32, the second added into the first), two Fp products per Fp coordinate for the scaled
+        abscissae of a chain's table; then the tree."""
     dbl, madd, add = GSUM_OPS[kind]
+    if (kind, impl) in GSUM_DIGIT_CHAINS:
+        chains, steps = GSUM_DIGIT_CHAINS[(kind, impl)]
+        table = 2 if kind == "g1" else 4
+        per_chain = steps * (dbl + GSUM_DIGIT_ADD_RATE * madd) + table
+        return L * chains * per_chain + L * (chains - 1) * add + (L - 1) * add
     if impl == "chain":
         if kind == "g1":
             return L * (128 * dbl + 64 * madd) + (L - 1) * add
@@ -242,8 +255,14 @@ def group_sum_ops(kind, impl, L):
 def group_sum_critical_path(kind, impl, L):
     """Fp-product times of the longest lane of one tile's workgroup.  Under SIMT a lane executes a
     masked addition whenever any lane of its wave takes it, so a chain pays the addition at every bit
-    and a bucket lane at every term."""
+    and a bucket lane at every term.  A digit form's joint chain pays it at every step the same way."""
     dbl, madd, add = GSUM_OPS[kind]
+    if (kind, impl) in GSUM_DIGIT_CHAINS:
+        chains, steps = GSUM_DIGIT_CHAINS[(kind, impl)]
+        width = 64
+        while width < L:
+            width *= 2
+        return steps * (dbl + madd) + (chains - 1) * add + (width.bit_length() - 1) * add
     if impl == "chain":
         width = 64
         while width < L:

@@ -250,6 +250,33 @@ int hbh_verify_dec_shares_grouped(hbh_engine* eng, size_t n, const uint8_t* shar
 #define HBH_AUTO_GSUM_G1_BUCKET_MIN 0
 #define HBH_AUTO_GSUM_G2_BUCKET_MIN 0
 int hbh_engine_set_group_sum_impl(hbh_engine* eng, int impl);
+/* How a grouped call READS and DRAWS its scalars (still 16 bytes per item; |x| = 0xd201000000010000 is the
+ * curve parameter, r = |x|^4 - |x|^2 + 1 the group order):
+ *   HBH_GSCALAR_INT128 (the default): one little-endian integer r_i < 2^128, as described above.
+ *   HBH_GSCALAR_DIGITS: short little-endian digits in the endomorphism basis (k_rlc_digits.hip):
+ *     hbh_verify_sig_shares_grouped reads X4: four u32 digits a0..a3,
+ *         r_i = a0 + a1 |x| + a2 |x|^2 + a3 |x|^3          <= (2^32 - 1)(1 + |x| + |x|^2 + |x|^3) < 2^224 < r;
+ *     hbh_verify_dec_shares_grouped reads X2: two u64 digits b0, b1,
+ *         r_i = b0 + b1 |x|^2                              <= (2^64 - 1)(1 + |x|^2) < 2^192 < r.
+ *     The integer r_i is below r, so it is its own residue, and the digits are below |x| (X4) / |x|^2 (X2),
+ *     so the base-|x| (base-|x|^2) representation is unique: distinct tuples are distinct residues mod r.
+ *     The all-zero tuple is excluded exactly as the zero scalar is (redrawn when the engine draws, HBH_ERR_ARG
+ *     when given), so the engine's draw is uniform over 2^128 - 1 distinct non-zero residues and the bound
+ *     above -- at most 1 / (2^128 - 1) per group holding an invalid share -- holds under the same conditions,
+ *     read for the form's digits: uniform non-zero tuples, independent of the inputs, unknown to whoever
+ *     chose the shares.  (The bound needs only that the r_i of a group's other items fix at most one
+ *     residue for which the group's equation holds.)  Both sums of a call use the SAME residue r_i for item i:
+ *     a signature call applies the X4 residue on its G1 side (as (a0 + a1 |x|) P + (a2 + a3 |x|) [x^2] P) and
+ *     on its G2 side (as a0 Q - a1 psi(Q) + a2 psi^2(Q) - a3 psi^3(Q), psi = [x] on G2); a decryption call
+ *     applies the X2 residue on both G1 sides.  Every chain is then 32 (G2), 96 (G1, X4) or 64 (G1, X2) steps
+ *     of one joint double-and-add instead of 64 + 64 (G2) or 128 (G1).
+ * Given scalars are used as given in the form's layout.  Verdicts of 0, the fallback, hbh_grouped_stats and the
+ * stage accounting do not depend on the form.  hbh_engine_set_group_sum_impl governs INT128 only: the digit
+ * forms always run their own kernels.  Any other value returns HBH_ERR_ARG and changes nothing.  Measured
+ * against INT128 and the per-share call: profiles/r22/README.md (tools/grouped_bench.py --scalar-form both). */
+#define HBH_GSCALAR_INT128 0
+#define HBH_GSCALAR_DIGITS 1
+int hbh_engine_set_group_scalar_form(hbh_engine* eng, int form);
 
 /* ---------------------------------------------------------------- combine (interpolate at 0)
  * threshold_crypto interpolate(t, samples) for `ncomb` independent combines of exactly t+1
@@ -610,6 +637,16 @@ int hbh_dbg_set_hash_rounds(hbh_engine* eng, int rounds);
  * written); scalars: n x 16 bytes little-endian, any value.  A group index >= ngroups is HBH_ERR_ARG. */
 int hbh_dbg_group_sums(hbh_engine* eng, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts, size_t ngroups,
                        const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1, uint8_t* out_g2);
+/* hbh_dbg_group_sums_form: the same sums with the scalars read in `form`: HBH_GFORM_INT128 (the bytes of
+ * hbh_dbg_group_sums), HBH_GFORM_X4 or HBH_GFORM_X2 (the digit layouts of HBH_GSCALAR_DIGITS; any tuple, the
+ * all-zero one contributes O).  The other arguments and the error rules are those of hbh_dbg_group_sums;
+ * X2 with a G2 list, and any other form, are HBH_ERR_ARG (no call sums G2 points under X2). */
+#define HBH_GFORM_INT128 0
+#define HBH_GFORM_X4 1
+#define HBH_GFORM_X2 2
+int hbh_dbg_group_sums_form(hbh_engine* eng, int form, size_t n, const uint8_t* g1_pts, const uint8_t* g2_pts,
+                            size_t ngroups, const uint32_t* group_idx, const uint8_t* scalars, uint8_t* out_g1,
+                            uint8_t* out_g2);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,17 @@ the HBH_STAGE_CURVE time per kind of sum and form that the AUTO thresholds are d
 include/hbbft_hip.h: the smallest swept size from which BUCKET's median is below CHAIN's by more than both
 cells' min-max spread, at that and every larger swept size).  The JSON is then {"cells", "sums", "auto"}.
 
-    python tools/grouped_bench.py --sum-impl both --reps 7 --out profiles/r17"""
+    python tools/grouped_bench.py --sum-impl both --reps 7 --out profiles/r17
+
+--scalar-form digits runs the grouped call under the digit form of its scalars
+(hbh_engine_set_group_scalar_form: X4 for signature shares, X2 for decryption shares; its own sum kernels);
+--scalar-form both runs it under the INT128 and the digit form in turn in this process, cell by cell, one
+more column per form, and judges each cell: the digit form WINS against a yardstick (the INT128 grouped
+call, the per-share call) when its median wall time is below the yardstick's by more than both cells'
+min-max spread, LOSES when it is above by more than both, TIES otherwise.  Not combined with --sum-impl
+(which governs the INT128 form only).
+
+    python tools/grouped_bench.py --scalar-form both --reps 7 --out profiles/r22"""
 import argparse
 import json
 import os
@@ -33,7 +43,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import bls12_381 as C  # noqa: E402
-from hbbft_amd._lib import GSUM_AUTO, GSUM_BUCKET, GSUM_CHAIN, STAGE_CURVE, STAGE_PAIRING, STAGE_PREPARE  # noqa: E402
+from hbbft_amd._lib import (GSCALAR_DIGITS, GSCALAR_INT128, GSUM_AUTO, GSUM_BUCKET, GSUM_CHAIN, STAGE_CURVE,  # noqa: E402
+                            STAGE_PAIRING, STAGE_PREPARE)
 from hbbft_amd.engine import Engine, g1_abi_from_uncompressed as g1a, g2_abi_from_uncompressed as g2a  # noqa: E402
 
 R = C.R
@@ -46,8 +57,12 @@ SHAPES = [  # (kind, shares, groups)
     ("decrypt", 65536, 1024),
     ("decrypt", 10000, 100),
 ]
-FORMS = {None: [("grouped", GSUM_AUTO)], "chain": [("grouped", GSUM_CHAIN)], "bucket": [("grouped", GSUM_BUCKET)],
-         "both": [("grouped_chain", GSUM_CHAIN), ("grouped_bucket", GSUM_BUCKET)]}
+# (column, (form of the group sums, form of the scalars)) of each grouped call of a cell
+FORMS = {None: [("grouped", (GSUM_AUTO, GSCALAR_INT128))], "chain": [("grouped", (GSUM_CHAIN, GSCALAR_INT128))],
+         "bucket": [("grouped", (GSUM_BUCKET, GSCALAR_INT128))],
+         "both": [("grouped_chain", (GSUM_CHAIN, GSCALAR_INT128)), ("grouped_bucket", (GSUM_BUCKET, GSCALAR_INT128))]}
+SCALAR_FORMS = {"int128": [("grouped", (GSUM_AUTO, GSCALAR_INT128))], "digits": [("grouped", (GSUM_AUTO, GSCALAR_DIGITS))],
+                "both": [("grouped_int128", (GSUM_AUTO, GSCALAR_INT128)), ("grouped_digits", (GSUM_AUTO, GSCALAR_DIGITS))]}
 MIXES = [("all valid", 0.0), ("1 % of groups bad", 0.01), ("10 % of groups bad", 0.10)]
 
 
@@ -110,11 +125,13 @@ def measure(eng, kind, n, ngroups, mix, frac, reps, rng, forms):
     args = inp["args"]
 
     def grouped(impl):
-        eng.set_group_sum_impl(impl)
+        eng.set_group_sum_impl(impl[0])
+        eng.set_group_scalar_form(impl[1])
         try:
             return grouped_call(*args)
         finally:
             eng.set_group_sum_impl(GSUM_AUTO)
+            eng.set_group_scalar_form(GSCALAR_INT128)
 
     want = plain(*args)  # first calls: verdicts, and the warm-up of every path
     assert want == inp["want"], "verdicts differ"
@@ -206,6 +223,28 @@ def fmt(c):
     return "%.2f / %.2f / %.2f" % (c["min"], c["median"], c["max"])
 
 
+def judge(new, old):
+    """'wins' / 'loses' when the medians differ by more than both cells' min-max spread, else 'ties'"""
+    gain = old["median"] - new["median"]
+    spread = max(new["max"] - new["min"], old["max"] - old["min"])
+    return "wins" if gain > spread else "loses" if -gain > spread else "ties"
+
+
+def judged_table(rows):
+    """--scalar-form both: the digit form against the INT128 grouped call and the per-share call"""
+    out = ["| shape | mix | INT128 / digits (medians) | digits vs INT128, beyond the spread | per-share / digits (medians) "
+           "| digits vs per-share, beyond the spread | CURVE ms INT128 / digits (medians) |", "|---|---|---|---|---|---|---|"]
+    for r in rows:
+        w, d = r["wall_ms"], r["device_ms"]
+        r["digits_vs_int128"] = judge(w["grouped_digits"], w["grouped_int128"])
+        r["digits_vs_per_share"] = judge(w["grouped_digits"], w["per_share"])
+        out.append("| %s %d in %d | %s | %.2f | %s | %.2f | %s | %.2f / %.2f |" % (
+            r["kind"], r["shares"], r["groups"], r["mix"], w["grouped_int128"]["median"] / w["grouped_digits"]["median"],
+            r["digits_vs_int128"], w["per_share"]["median"] / w["grouped_digits"]["median"], r["digits_vs_per_share"],
+            d["curve_int128"]["median"], d["curve_digits"]["median"]))
+    return "\n".join(out) + "\n"
+
+
 def table(rows, forms):
     tails = [f[len("grouped"):] for f, _ in forms]
     head = ["shape", "mix", "fallback items", "per-share wall ms"]
@@ -246,10 +285,14 @@ def main():
     ap.add_argument("--only", type=int, default=None, help="index of one shape (rehearsal)")
     ap.add_argument("--sum-impl", choices=["chain", "bucket", "both"], default=None,
                     help="form of the group sums (default: the engine's AUTO)")
+    ap.add_argument("--scalar-form", choices=["int128", "digits", "both"], default=None,
+                    help="form of the grouped call's scalars (default: int128)")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
-    forms = FORMS[a.sum_impl]
+    if a.sum_impl and a.scalar_form:
+        ap.error("--sum-impl governs the INT128 form only: not combined with --scalar-form")
+    forms = SCALAR_FORMS[a.scalar_form] if a.scalar_form else FORMS[a.sum_impl]
     eng = Engine(0)
     rng = random.Random(16)
     rows, sums = [], []
@@ -266,6 +309,9 @@ def main():
     eng.close()
     md = "min / median / max of %d alternated runs per cell\n\n" % a.reps + table(rows, forms)
     doc = rows
+    if a.scalar_form == "both":
+        md += "\nThe digit form against its yardsticks (wall time; wins / loses: beyond both cells' min-max spread)\n\n"
+        md += judged_table(rows)
     if a.sum_impl == "both":
         auto = auto_thresholds(sums)
         md += "\nThe sums alone (hbh_dbg_group_sums, one side per call; device ms under HBH_STAGE_CURVE)\n\n" + sums_table(sums, auto)
