@@ -115,6 +115,121 @@ HP_D Fp h_sqr(const Fp& a) {
   return fp_mul(x, y);
 }
 
+// The squaring of a + b s in Fp4 = Fp2[s] / (s^2 - xi), the block of the cyclotomic squarings
+// (h12_cyclo_sqr, hc_sqr): A = a^2 + xi b^2, B = 2 a b = (a + b)^2 - a^2 - b^2.  HP_SQR4 = 1 takes
+// it in one leaf (h_sqr4_l) with two Montgomery reductions, one per output, on the unreduced sums;
+// 0 keeps three h_sqr, each with a reduction of its own (A/B: profiles/r23).
+#ifndef HP_SQR4
+#define HP_SQR4 1
+#endif
+#if HP_SQR4
+typedef int32_t V28 __attribute__((ext_vector_type(2 * NL)));  // returns in v0..v27
+
+// own components of (A, B): limbs 0..13 of the result are A's, 14..27 B's.
+// Contract: a, b normalised, |.| < 2p -> A normalised, in (-p/20, p + p/20); B lazy, |limb| < 2^28
+// (the top one < 2^19), |B| < 1.1p: an operand of fp_red_mk and h_add_xi_l, as the callers use it.
+//
+// The three squares are h_sqr's products x y with (x, y) = (a0 + a1, a0 - a1) on the even lane and
+// (2 a0, a1) on the odd one: |x_i| < 2^29, |y_i| < 2^28 for a and for b, and the pair of a + b is the
+// limb-wise sum of the two, |x_i| <= 2^30 - 4, |y_i| <= 2^29 - 2, not normalised.  They are product
+// scans without Montgomery digits of their own.  With S(.) the unreduced squares and S'(b) the
+// partner's component of S(b), xi (g + h u) = (g - h) + (g + h) u gives
+//   A = S(a) + S(b) -/+ S'(b),  C = A + B = S(a + b) -/+ S'(b)     (even lane - , odd lane +)
+// so only S(b) has to cross the lane pair.  Its chain alone is carry-extracted, column by column, to
+// 28-bit limbs, which travel as one v_mov_dpp each; S(a)'s and S(a + b)'s products go straight into
+// the Montgomery accumulators of A and C (fp_mul_l's digits and columns) together with those limbs.
+// Montgomery reduction is linear, so B = C - A limb by limb.  Three MAD chains of products, two of
+// digits; no 28-limb value is stored.
+// int64: a column of A is < 14 x 2^57 + 14 x 2^56 + 2^30 and one of C < 14 x 2^59 + 14 x 2^56 + 2^29,
+// with carries < 2^36: < 2^62.98, inside int64 because the product chain of a + b is the only one
+// at 2^59 per term and the digits' terms are 2^56.  The unreduced sums are |A| < 48 p^2 and |C| < 80
+// p^2, so the outputs (T + m P) / R with 0 <= m < R lie in (-80 p^2 / R, p + 80 p^2 / R), and p / R <
+// 2^-11.  The headroom in C's accumulator is 1.6 %, and it rests on the operand pair of a + b staying
+// within 2^30 - 4 and 2^29 - 2: a and b MUST be normalised (limbs 0..12 in [0, 2^28)), not merely
+// |.| < 2p -- a lazy operand, which h_mul takes, overflows the int64 here without a sign of it.
+// (tests/test_pair_sqr4_model.py restates this function statement by statement.)
+HS_MULFN V28 h_sqr4_l(HS_P14(x), HS_P14(y)) {
+  const Fp a = {{HS_L14(x)}};
+  const Fp b = {{HS_L14(y)}};
+  const int32_t sm = lp_even() ? -1 : 0;  // the even lane subtracts the partner's component
+  int32_t xa[NL], ya[NL], xb[NL], yb[NL], xs[NL], ys[NL];
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    // x = a0 + partner's: a0 + a1 on the even lane, a0 + a0 on the odd; y = a - (even ? a1 : 0)
+    const int32_t pa = dpp<DPP_SWAP>(a.l[i]), pb = dpp<DPP_SWAP>(b.l[i]);
+    xa[i] = dpp<DPP_EVEN>(a.l[i]) + pa;
+    ya[i] = a.l[i] - (pa & sm);
+    xb[i] = dpp<DPP_EVEN>(b.l[i]) + pb;
+    yb[i] = b.l[i] - (pb & sm);
+    xs[i] = xa[i] + xb[i];
+    ys[i] = ya[i] + yb[i];
+  }
+  int32_t mA[NL], mC[NL], A[NL], C[NL];
+  int64_t cb = 0, ra = 0, rc = 0;
+#pragma unroll
+  for (int k = 0; k < 2 * NL - 1; k++) {
+#pragma unroll
+    for (int i = (k < NL ? 0 : k - NL + 1); i <= (k < NL ? k : NL - 1); i++) {
+      ra += (int64_t)xa[i] * ya[k - i];
+      cb += (int64_t)xb[i] * yb[k - i];
+      rc += (int64_t)xs[i] * ys[k - i];
+    }
+    const int32_t lb = (int32_t)cb & MASK28;
+    cb >>= 28;
+    const int32_t w = (dpp<DPP_SWAP>(lb) ^ sm) - sm;
+    ra += lb + w;
+    rc += w;
+    if (k < NL) {
+#pragma unroll
+      for (int i = 0; i < k; i++) {
+        ra += (int64_t)mA[i] * (int32_t)P_L[k - i];
+        rc += (int64_t)mC[i] * (int32_t)P_L[k - i];
+      }
+      mA[k] = mont_digit(ra);
+      mC[k] = mont_digit(rc);
+      ra += (int64_t)mA[k] * (int32_t)P_L[0];
+      rc += (int64_t)mC[k] * (int32_t)P_L[0];
+    } else {
+#pragma unroll
+      for (int i = k - NL + 1; i < NL; i++) {
+        ra += (int64_t)mA[i] * (int32_t)P_L[k - i];
+        rc += (int64_t)mC[i] * (int32_t)P_L[k - i];
+      }
+      A[k - NL] = (int32_t)ra & MASK28;
+      C[k - NL] = (int32_t)rc & MASK28;
+    }
+    ra >>= 28;
+    rc >>= 28;
+  }
+  // limb 27: the chains' last carries
+  const int32_t tb = (int32_t)cb;
+  const int32_t tw = (dpp<DPP_SWAP>(tb) ^ sm) - sm;
+  A[NL - 1] = (int32_t)ra + tb + tw;
+  C[NL - 1] = (int32_t)rc + tw;
+  V28 r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    r[i] = A[i];
+    r[NL + i] = C[i] - A[i];
+  }
+  return r;
+}
+
+// B is lazy (signed limbs, not normalised): it must go through a carry pass (fp_red_mk, fp_norm)
+// before it is the operand of any product
+struct Sq4 { Fp A, B; };
+HP_D Sq4 h_sqr4(const Fp& a, const Fp& b) {
+  const V28 v = h_sqr4_l(HS_E14(a), HS_E14(b));
+  Sq4 r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    r.A.l[i] = v[i];
+    r.B.l[i] = v[NL + i];
+  }
+  return r;
+}
+#endif
+
 // a * (1 + u): even a0 - a1, odd a1 + a0
 HP_D Fp h_mul_xi(const Fp& a) {
   const int32_t sm = lp_even() ? -1 : 0;
@@ -561,6 +676,27 @@ HP_D H12 h12_cyclo_sqr(const H12& f) {
   const Fp& a0 = f.c0.c0; const Fp& a2 = f.c0.c1; const Fp& a4 = f.c0.c2;
   const Fp& a1 = f.c1.c0; const Fp& a3 = f.c1.c1; const Fp& a5 = f.c1.c2;
   H12 r;
+#if HP_SQR4
+  // h_sqr4: A normalised, in (-p/20, 21p/20), inside h_sqr's (-p/8, 9p/8); B lazy, |limb| < 2^28, |B| <
+  // 1.1p.  Into the passes: |3 A - 2 a| < 3.15p + 4p, |3 B + 2 a| < 3.3p + 4p, and with xi on B (|limb|
+  // < 2^29, |.| < 2.2p) < 6.6p + 4p: under fp_red_mk's 64p with |t_i| < 2^31; outputs in (-p/1000, p +
+  // p/1000), reduced
+  {
+    const Sq4 s = h_sqr4(a0, a3);
+    r.c0.c0 = fp_red_mk<3, -2>(s.A, a0);
+    r.c1.c1 = fp_red_mk<3, 2>(s.B, a3);
+  }
+  {
+    const Sq4 s = h_sqr4(a1, a4);
+    r.c0.c1 = fp_red_mk<3, -2>(s.A, a2);
+    r.c1.c2 = fp_red_mk<3, 2>(s.B, a5);
+  }
+  {
+    const Sq4 s = h_sqr4(a2, a5);
+    r.c0.c2 = fp_red_mk<3, -2>(s.A, a4);
+    r.c1.c0 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), s.B), a1);
+  }
+#else
   {
     const Fp s0 = h_sqr(a0), s3 = h_sqr(a3), s03 = h_sqr(fp_add(a0, a3));
     r.c0.c0 = fp_red_mk<3, -2>(h_add_xi_l(s0, s3), a0);
@@ -576,6 +712,7 @@ HP_D H12 h12_cyclo_sqr(const H12& f) {
     r.c0.c2 = fp_red_mk<3, -2>(h_add_xi_l(s2, s5), a4);
     r.c1.c0 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), fp_sub2l(s25, s2, s5)), a1);
   }
+#endif
   return r;
 }
 
@@ -590,9 +727,22 @@ HP_D H12 h12_cyclo_sqr(const H12& f) {
 struct HC { Fp a1, a2, a4, a5; };
 
 HP_D HC hc_compress(const H12& f) { return {f.c1.c0, f.c0.c1, f.c0.c2, f.c1.c2}; }
-// input reduced, output reduced: h12_cyclo_sqr's formulas, bounds and carry passes
+// input reduced, output reduced: h12_cyclo_sqr's formulas, bounds and carry passes (with HP_SQR4,
+// the bounds in the comment at the head of its HP_SQR4 branch: 3 A - 2 a_k, 3 B + 2 a_k, and xi on B)
 HP_D HC hc_sqr(const HC& c) {
   HC r;
+#if HP_SQR4
+  {
+    const Sq4 s = h_sqr4(c.a1, c.a4);
+    r.a2 = fp_red_mk<3, -2>(s.A, c.a2);
+    r.a5 = fp_red_mk<3, 2>(s.B, c.a5);
+  }
+  {
+    const Sq4 s = h_sqr4(c.a2, c.a5);
+    r.a4 = fp_red_mk<3, -2>(s.A, c.a4);
+    r.a1 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), s.B), c.a1);
+  }
+#else
   {
     const Fp s1 = h_sqr(c.a1), s4 = h_sqr(c.a4), s14 = h_sqr(fp_add(c.a1, c.a4));
     r.a2 = fp_red_mk<3, -2>(h_add_xi_l(s1, s4), c.a2);
@@ -603,6 +753,7 @@ HP_D HC hc_sqr(const HC& c) {
     r.a4 = fp_red_mk<3, -2>(h_add_xi_l(s2, s5), c.a4);
     r.a1 = fp_red_mk<3, 2>(h_add_xi_l(fp_zero(), fp_sub2l(s25, s2, s5)), c.a1);
   }
+#endif
   return r;
 }
 // the denominator 4 a1 of a3: a1 reduced -> normalised, |.| < 8p (a product operand)
