@@ -68,6 +68,7 @@ SIGNATURES = [
     ("hbh_engine_set_ack_impl", _I, [_P, _I]),
     ("hbh_engine_set_decode_impl", _I, [_P, _I]),
     ("hbh_engine_set_hash_impl", _I, [_P, _I]),
+    ("hbh_engine_set_hash_form", _I, [_P, _I]),
     ("hbh_dbg_set_hash_rounds", _I, [_P, _I]),
     # hashing to G2 on the device
     ("hbh_engine_hash_g2", _I, [_P, _SZ, _P, _P, _P]),
@@ -124,7 +125,10 @@ DEC_AUTO, DEC_LANE, DEC_SPLIT = 0, 1, 2  # HBH_DEC_*
 AUTO_DEC_G1_SPLIT_MAX, AUTO_DEC_G2_SPLIT_MAX = 8192, 8192  # HBH_AUTO_DEC_G*_SPLIT_MAX
 HASH_AUTO, HASH_HOST, HASH_DEVICE = 0, 1, 2  # HBH_HASH_*
 HASH_ROUNDS = 32  # HBH_HASH_ROUNDS
-AUTO_HASH_DEVICE_MIN = 4096  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r14)
+AUTO_HASH_DEVICE_MIN = 384  # HBH_AUTO_HASH_DEVICE_MIN (profiles/r24: the quad form beats the host stage from here)
+HFORM_AUTO, HFORM_LANE, HFORM_QUAD = 0, 1, 2  # HBH_HFORM_*: lanes per message of the device hash
+HASH_QUAD_ALL = 2**64 - 1  # HBH_HASH_QUAD_ALL: the value of AUTO_HASH_QUAD_MAX that means every size
+AUTO_HASH_QUAD_MAX = HASH_QUAD_ALL  # HBH_AUTO_HASH_QUAD_MAX (0: never; profiles/r24: QUAD wins at every swept size)
 GSUM_AUTO, GSUM_CHAIN, GSUM_BUCKET = 0, 1, 2  # HBH_GSUM_*
 AUTO_GSUM_G1_BUCKET_MIN, AUTO_GSUM_G2_BUCKET_MIN = 0, 0  # HBH_AUTO_GSUM_G*_BUCKET_MIN (0: never; profiles/r17)
 GSCALAR_INT128, GSCALAR_DIGITS = 0, 1  # HBH_GSCALAR_*: how a grouped call reads and draws its scalars

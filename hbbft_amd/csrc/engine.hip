@@ -123,6 +123,7 @@ struct hbh_engine {
   int gscalar_form = HBH_GSCALAR_INT128;  // how the grouped share checks read and draw scalars (hbh_engine_set_group_scalar_form)
   int hash_impl = HBH_HASH_AUTO;  // where the curve half of hash_g2 runs (hbh_engine_set_hash_impl)
   int hash_rounds = HBH_HASH_ROUNDS;  // sampler rounds of the device form (hbh_dbg_set_hash_rounds)
+  int hash_form = HBH_HFORM_AUTO;  // lanes per message of the device form (hbh_engine_set_hash_form)
   StageTimer timer;
   // Completion of the last call's device work on whichever stream it ran.  Every call waits for it
   // on its own stream before touching the engine-owned workspaces, so a _dev call on a caller
@@ -723,6 +724,15 @@ int hbh_engine_set_hash_impl(hbh_engine* e, int impl) {
   return HBH_OK;
 }
 
+int hbh_engine_set_hash_form(hbh_engine* e, int form) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (form != HBH_HFORM_AUTO && form != HBH_HFORM_LANE && form != HBH_HFORM_QUAD)
+    return fail(HBH_ERR_ARG, "unknown hash-to-G2 device form");
+  std::lock_guard<std::mutex> lk(e->mu);
+  e->hash_form = form;
+  return HBH_OK;
+}
+
 int hbh_dbg_set_hash_rounds(hbh_engine* e, int rounds) {
   if (!e) return fail(HBH_ERR_ARG, "null engine");
   if (rounds < 0 || rounds > 1024) return fail(HBH_ERR_ARG, "hash rounds out of range");
@@ -783,13 +793,20 @@ bool hash_on_device(const hbh_engine* e, size_t n) {
   return HBH_AUTO_HASH_DEVICE_MIN != 0 && n >= HBH_AUTO_HASH_DEVICE_MIN;
 }
 
+// which device form a run of n messages takes (hbh_engine_set_hash_form); same bytes from either
+bool hash_quad(const hbh_engine* e, size_t n) {
+  if (e->hash_form != HBH_HFORM_AUTO) return e->hash_form == HBH_HFORM_QUAD;
+  return HBH_AUTO_HASH_QUAD_MAX != 0 && n <= HBH_AUTO_HASH_QUAD_MAX;
+}
+
 // the kernels of the device form on s: d_seeds -> d_out, one state byte per message in e->hash_state
 int launch_hash(hbh_engine* e, hipStream_t s, size_t n, const uint8_t* d_seeds, void* d_out,
                 hbl::HashForm form = hbl::HASH_FORM_FULL) {
   HBH_CHECK(e->hash_work.ensure(hbl::hash_work_bytes(n, e->hash_rounds)));
   HBH_CHECK(e->hash_state.ensure(n));
   StageScope tm(e, s, HBH_STAGE_HASH);
-  HBH_CHECK(hbl::hash_g2(s, (int)n, e->hash_rounds, d_seeds, e->hash_work.p, (uint8_t*)e->hash_state.p, d_out, form));
+  const auto run = hash_quad(e, n) ? hbl::hash_g2_quad : hbl::hash_g2;
+  HBH_CHECK(run(s, (int)n, e->hash_rounds, d_seeds, e->hash_work.p, (uint8_t*)e->hash_state.p, d_out, form));
   return HBH_OK;
 }
 

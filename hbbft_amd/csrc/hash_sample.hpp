@@ -133,4 +133,16 @@ HB_HD bool gen_fq(Stream& s, uint32_t w[12], int max_draws = 64) {
   return false;
 }
 
+// Step over one candidate of G2::rand -- x = (gen_fq, gen_fq) and the sign flag -- without keeping
+// it: the stream stands where drawing the candidate would have left it.  No field work.  false on
+// gen_fq's draw failure (the stream then stands behind the failed draws, as gen_fq leaves it).
+// k_hash_quad.hip opens a message's stream at its saved position on four lanes and steps lane j over
+// j candidates, so that the lanes try the next four side by side.
+HB_HD bool skip_candidate(Stream& s, int max_draws = 64) {
+  uint32_t w[12];
+  if (!gen_fq(s, w, max_draws) || !gen_fq(s, w, max_draws)) return false;
+  (void)gen_bool(s);
+  return true;
+}
+
 }  // namespace hsample

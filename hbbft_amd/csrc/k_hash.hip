@@ -26,6 +26,7 @@
 
 #include "curve.hpp"
 #include "hash_sample.hpp"
+#include "hash_work.hpp"
 #include "launch.hpp"
 #include "wire_root.hpp"
 
@@ -35,8 +36,6 @@ namespace hb {
 __device__ __forceinline__ Fp fq_limbs_to_fp(const uint32_t w[12]) {
   return fp_mul(fp_limbs_from_words(w), fp_const(FQ_RAND_M));
 }
-
-constexpr int XY_WORDS = 4 * NL;  // a sampled point between the kernels: x.c0, x.c1, y.c0, y.c1 (Montgomery limbs)
 
 __global__ void __launch_bounds__(64) k_hash_sample(int n, const uint32_t* __restrict__ count,
                                                     const uint32_t* __restrict__ list,
@@ -203,26 +202,6 @@ __global__ void __launch_bounds__(64) k_hash_clear_bp(int n, const uint32_t* __r
 }  // namespace hb
 
 namespace hbl {
-
-namespace {
-constexpr int HASH_RETRY_ROUNDS = 2;  // sampler rounds for messages k_hash_clear sent back
-struct HashWork {
-  uint32_t *counts, *pos, *xy, *list[2], *retry;
-};
-// one count per round, the retry count and one per retry round, padded to four words
-size_t hash_count_words(int rounds) { return ((size_t)rounds + 2 + HASH_RETRY_ROUNDS + 3) & ~(size_t)3; }
-// counts and pos first: one memset zeroes both
-HashWork hash_carve(void* work, size_t n, int rounds) {
-  HashWork w;
-  w.counts = (uint32_t*)work;
-  w.pos = w.counts + hash_count_words(rounds);
-  w.xy = w.pos + 2 * n;
-  w.list[0] = w.xy + (size_t)hb::XY_WORDS * n;
-  w.list[1] = w.list[0] + n;
-  w.retry = w.list[1] + n;
-  return w;
-}
-}  // namespace
 
 size_t hash_work_bytes(size_t n, int rounds) {
   return (hash_count_words(rounds) + (2 + (size_t)hb::XY_WORDS + 3) * n) * sizeof(uint32_t);

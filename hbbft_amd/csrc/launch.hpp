@@ -200,5 +200,11 @@ enum HashForm { HASH_FORM_FULL = 0, HASH_FORM_BP = 1 };
 size_t hash_work_bytes(size_t n, int rounds);
 hipError_t hash_g2(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out,
                    HashForm form = HASH_FORM_FULL);
+// The latency form (k_hash_quad.hip, HBH_HFORM_QUAD): four lanes per message -- the sampler tries four
+// candidates per launch, the cofactor multiplication runs on lane quads.  Same arguments, work layout,
+// state bytes and output bytes as hash_g2.  `rounds` stays a cap on CANDIDATES (ceil(rounds / 4) sampler
+// launches, the last one masked to the remainder), so both forms leave the same messages unresolved.
+hipError_t hash_g2_quad(hipStream_t s, int n, int rounds, const uint8_t* seeds, void* work, uint8_t* state, void* out,
+                        HashForm form = HASH_FORM_FULL);
 
 }  // namespace hbl

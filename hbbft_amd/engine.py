@@ -261,6 +261,14 @@ class Engine:
         verify_ciphertexts_uv and encrypt; same bytes and verdicts either way."""
         check(self._l.hbh_engine_set_hash_impl(self._h, int(impl)))
 
+    def set_hash_form(self, form):
+        """HBH_HFORM_*: how the device runs a hash.  1 = one lane per message (the throughput form), 2 =
+        a lane quad per message (the latency form: four candidates per sampler launch, the cofactor
+        multiplication on lane quads), 0 = auto (default: the quad up to AUTO_HASH_QUAD_MAX messages).
+        Same bytes, the same messages left unresolved under a round cap; no effect on a call that
+        takes the host stage."""
+        check(self._l.hbh_engine_set_hash_form(self._h, int(form)))
+
     def dbg_set_hash_rounds(self, rounds):
         """Sampler rounds of the device hash (hbh_dbg_set_hash_rounds; 0 restores the default): tests only."""
         check(self._l.hbh_dbg_set_hash_rounds(self._h, int(rounds)))

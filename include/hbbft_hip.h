@@ -407,8 +407,8 @@ int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
  * the message assembly run on the host (hbh_hash_g2's code and worker threads); the curve half --
  * sampling x from the seeded ChaCha20 stream, the square root, the sign choice and the cofactor
  * multiplication (csrc/hash_sample.hpp, k_hash.hip) -- runs on the GPU.  Output bytes are hbh_hash_g2's.
- * This is a throughput form: one lane walks a whole hash, which takes milliseconds, so small calls
- * belong on the host stage (hbh_engine_set_hash_impl).
+ * A hash is a serial chain of milliseconds however many lanes walk it (one, or four: hbh_engine_set_hash_form),
+ * so small calls belong on the host stage (hbh_engine_set_hash_impl).
  *   hbh_engine_hash_g2 / hbh_engine_hash_g1_g2: arguments and output as hbh_hash_g2 / hbh_hash_g1_g2.
  *   hbh_hash_g2_dev: d_seeds = n 32-byte seeds (sha3_256 of each message) in HBM, d_out = n ABI G2 points
  *     in HBM; asynchronous on `stream` and ordered like the other _dev calls.  The sampler runs a fixed
@@ -425,8 +425,32 @@ int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
  *     never), HOST below.  Governs every host-pointer call of this section; same bytes and verdicts from
  *     either.
  *     Threshold: the smallest swept size from which DEVICE's median host-to-host time is below HOST's by
- *     more than both cells' min-max spread, at that and every larger swept size (profiles/r14/README.md,
- *     tools/hash_bench.py).  Any other value returns HBH_ERR_ARG and changes nothing.
+ *     more than both cells' min-max spread, at that and every larger swept size, DEVICE taking the better of
+ *     its two forms (384 with the QUAD form: profiles/r24/README.md; 4,096 with the LANE form alone:
+ *     profiles/r14/README.md; tools/hash_bench.py).  Any other value returns HBH_ERR_ARG and changes nothing.
+ *   hbh_engine_set_hash_form: how many lanes walk one hash when a call runs on the device.  HBH_HFORM_LANE
+ *     is the throughput form above (k_hash.hip).  HBH_HFORM_QUAD is its latency form (k_hash_quad.hip): four
+ *     lanes per message -- the sampler tries a message's next four candidates side by side, one launch for
+ *     15 messages in 16, and the cofactor multiplication runs on lane quads (the lane-pair Fp2 and group law
+ *     of the split decoders).  HBH_HFORM_AUTO (the default): QUAD for device runs of at most
+ *     HBH_AUTO_HASH_QUAD_MAX messages (0: never; HBH_HASH_QUAD_ALL: every size), LANE above.  Any other
+ *     value returns HBH_ERR_ARG and changes nothing.  A setter of its own: hbh_engine_set_hash_impl says
+ *     WHERE a call runs, this one HOW the device runs it, and it has no effect on a call that takes the host
+ *     stage.  It governs every device run of the hash: hbh_engine_hash_g2 / _hash_g1_g2 / _hash_g1_g2_bp,
+ *     hbh_hash_g2_dev, hbh_verify_signatures, hbh_verify_ciphertexts_uv and hbh_engine_encrypt; each still
+ *     records one HBH_STAGE_HASH entry per call.
+ *     Bytes: QUAD writes LANE's and the host stage's bytes, in the full and in the Q form.
+ *     Round cap: HBH_HASH_ROUNDS (and hbh_dbg_set_hash_rounds) caps the CANDIDATES tried per message under
+ *     either form -- QUAD runs ceil(cap / 4) sampler launches and masks the lanes whose candidate would be
+ *     past the cap -- so both forms leave exactly the same messages unresolved, and hbh_hash_g2_dev writes
+ *     the same bytes, zero points included, under either.
+ *     Thresholds: a form wins at a size when the other's median host-to-host time exceeds its own by more
+ *     than the two cells' min-max spreads together.  HBH_AUTO_HASH_QUAD_MAX is the largest swept size up to
+ *     which QUAD wins at every swept size from the smallest; HBH_AUTO_HASH_DEVICE_MIN is the smallest swept
+ *     size from which the better device form beats HOST at that and every larger one.  The sweep of
+ *     profiles/r24/README.md (tools/hash_bench.py --form both; sizes 64 .. 65,536) set them: QUAD wins at every
+ *     size (hash stage 4.5 against 14.1 ms at 64 messages, 7.2 against 23.3 ms at 10,100, 18.8 against 26.4 ms
+ *     at 65,536), so HBH_AUTO_HASH_QUAD_MAX is HBH_HASH_QUAD_ALL, and HBH_AUTO_HASH_DEVICE_MIN is 384 (refined between the swept 256 and 1,024).
  * The Q form (k_hash_clear_bp): the device stops at the Budroni-Pintore image Q_bp of the sampled point,
  * hash_g1_g2(U, V) = [KCOF] Q_bp (hbh_hash_g1_g2_bp below), for the callers that fold [KCOF] into a pairing
  * side or into a scalar they multiply by anyway.  HOST, DEVICE and AUTO as above; messages left after
@@ -445,7 +469,13 @@ int hbh_engine_set_decode_impl(hbh_engine* eng, int impl);
 #define HBH_HASH_HOST 1
 #define HBH_HASH_DEVICE 2
 #define HBH_HASH_ROUNDS 32
-#define HBH_AUTO_HASH_DEVICE_MIN 4096
+#define HBH_AUTO_HASH_DEVICE_MIN 384 /* profiles/r24 (the QUAD form; 4,096 with the LANE form alone, profiles/r14) */
+#define HBH_HFORM_AUTO 0
+#define HBH_HFORM_LANE 1
+#define HBH_HFORM_QUAD 2
+#define HBH_HASH_QUAD_ALL ((size_t)-1) /* a value of HBH_AUTO_HASH_QUAD_MAX: QUAD at every size */
+#define HBH_AUTO_HASH_QUAD_MAX (HBH_HASH_QUAD_ALL) /* QUAD wins at every swept size, 64 .. 65,536 (profiles/r24) */
+int hbh_engine_set_hash_form(hbh_engine* eng, int form);
 int hbh_engine_hash_g2(hbh_engine* eng, size_t n, const uint8_t* data, const size_t* offsets, uint8_t* out);
 int hbh_engine_hash_g1_g2(hbh_engine* eng, size_t n, const uint8_t* u, const uint8_t* data, const size_t* offsets,
                           uint8_t* out);

@@ -16,6 +16,10 @@ that size, then `reps` alternations timed host-to-host with profiling off; min /
   node round  bench.py's dkg_node_round restated (N = 100, t = 33, the same set-up and the same three timed
               steps) with SyncKeyGen(device_hash=False / True) under HBH_HASH_AUTO
 
+--form lane | quad | both picks the device form of the hash in the verify rows (hbh_engine_set_hash_form;
+default lane, the rows of profiles/r15); both times hbh_verify_ciphertexts_uv under LANE and under QUAD in
+the same alternation.
+
 A form wins a row when the other's median exceeds its own by more than both cells' min-max spreads together."""
 import argparse
 import ctypes
@@ -108,7 +112,9 @@ def encrypt_ab(eng, n, reps):
     return row, out["host"], offs
 
 
-def verify_ab(eng, n, reps, cts, offs):
+def verify_ab(eng, n, reps, cts, offs, form="lane"):
+    """form: the device form of the hash (hbh_engine_set_hash_form) of the "device" column -- lane or quad;
+    both adds a "quad" column beside the lane form's "device" """
     L = eng._l
     u, v, w = cts
     wb = bytearray(bytes(w))
@@ -120,22 +126,30 @@ def verify_ab(eng, n, reps, cts, offs):
     po = offs.ctypes.data_as(VP)
     g1k = cbuf(hoststage.hash_bp_g1() * n)
     q = (ctypes.c_uint8 * (192 * n))()
-    verdict = {k: (ctypes.c_uint8 * n)() for k in ("host", "device")}
+    hform = {"device": _lib.HFORM_QUAD if form == "quad" else _lib.HFORM_LANE}
+    if form == "both":
+        hform["quad"] = _lib.HFORM_QUAD
+    verdict = {k: (ctypes.c_uint8 * n)() for k in ("host", *hform)}
 
     def host():
         _lib.check_host(L.hbh_hash_g1_g2_bp(n, ptr(u), ptr(v), po, ptr(q), 0))
         _lib.check(L.hbh_verify_pairing_eq(eng.handle, n, ptr(g1k), ptr(w), n, None, ptr(u), ptr(q), n, None,
                                            ptr(verdict["host"])))
 
-    def device():
-        _lib.check(L.hbh_verify_ciphertexts_uv(eng.handle, n, ptr(u), ptr(v), po, ptr(w), ptr(verdict["device"])))
+    def device(k):
+        eng.set_hash_form(hform[k])
+        _lib.check(L.hbh_verify_ciphertexts_uv(eng.handle, n, ptr(u), ptr(v), po, ptr(w), ptr(verdict[k])))
 
+    forms = {"host": host, **{k: (lambda k=k: device(k)) for k in hform}}
     eng.set_hash_impl(_lib.HASH_DEVICE)
-    host()
-    device()
-    assert bytes(verdict["host"]) == want and bytes(verdict["device"]) == want, "verdicts differ from the construction"
-    row = {"n": n, **alternate({"host": host, "device": device}, reps)}
+    for k, fn in forms.items():
+        fn()
+        assert bytes(verdict[k]) == want, "verdicts differ from the construction (%s)" % k
+    row = {"n": n, **alternate(forms, reps)}
+    eng.set_hash_form(_lib.HFORM_AUTO)
     row["device_wins"] = wins(row["device"], row["host"])
+    if form == "both":
+        row["quad_beats_lane"] = wins(row["quad"], row["device"])
     return row
 
 
@@ -234,6 +248,14 @@ def tables(res):
         for r in res[name]:
             o.append("| %d | %s | %s | %s |" % (r["n"], fmt(r["host"]), fmt(r["device"]), "yes" if r["device_wins"] else "no"))
         o.append("")
+        if any("quad" in r for r in res[name]):
+            o.append("### %s, the device hash on lanes against lane quads\n\n| items | DEVICE-LANE ms (min / median / max) | "
+                     "DEVICE-QUAD ms (min / median / max) | QUAD wins |\n|---|---|---|---|" % name)
+            for r in res[name]:
+                if "quad" in r:
+                    o.append("| %d | %s | %s | %s |" % (r["n"], fmt(r["device"]), fmt(r["quad"]),
+                                                        "yes" if r["quad_beats_lane"] else "no"))
+            o.append("")
     o.append("### hash stage (HBH_STAGE_HASH device time)\n\n| seeds | Q form ms (min / median / max) | full form ms "
              "(min / median / max) | Q form wins |\n|---|---|---|---|")
     for r in res["hash_stage"]:
@@ -257,6 +279,8 @@ def main():
     ap.add_argument("--stage-sizes", default=",".join(str(s) for s in STAGE_SIZES))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--node-round", type=int, default=100, help="nodes of the node-round A/B, t = (N - 1) // 3 (0: skip)")
+    ap.add_argument("--form", choices=("lane", "quad", "both"), default="lane",
+                    help="device form of the hash in the verify rows (hbh_engine_set_hash_form); both: LANE against QUAD")
     ap.add_argument("--out", default=None, help="directory for dkg_crypto_bench.json and dkg_crypto_bench.md")
     a = ap.parse_args()
     eng = Engine(0)
@@ -268,10 +292,12 @@ def main():
             res["encrypt"].append(row)
             print("encrypt n %6d  host %s  device %s  %s" % (n, fmt(row["host"]), fmt(row["device"]),
                                                               "DEVICE" if row["device_wins"] else "-"), flush=True)
-            row = verify_ab(eng, n, a.reps, cts, offs)
+            row = verify_ab(eng, n, a.reps, cts, offs, a.form)
             res["verify"].append(row)
             print("verify  n %6d  host %s  device %s  %s" % (n, fmt(row["host"]), fmt(row["device"]),
-                                                              "DEVICE" if row["device_wins"] else "-"), flush=True)
+                                                              "DEVICE" if row["device_wins"] else "-") +
+                  ("  quad %s  %s" % (fmt(row["quad"]), "QUAD" if row["quad_beats_lane"] else "-") if "quad" in row else ""),
+                  flush=True)
         for n in [int(s) for s in a.stage_sizes.split(",") if s]:
             row = hash_stage(eng, n, a.reps)
             res["hash_stage"].append(row)

@@ -2,6 +2,7 @@
 
   python3 tools/hash_bench.py --out profiles/r14            the sweep + the verify_signed A/B
   python3 tools/hash_bench.py --sizes 1024,16384 --reps 9
+  python3 tools/hash_bench.py --form both --out profiles/r24   HOST, DEVICE-LANE and DEVICE-QUAD side by side
 
 For every size, hbh_engine_hash_g2 is forced to HOST and to DEVICE in turn (hbh_engine_set_hash_impl) on
 the same seeded 28-byte messages: one warm-up call of each form at that size, then `reps` alternations
@@ -13,7 +14,14 @@ worker count (hbh_host_threads).
 The AUTO threshold the sweep supports is the smallest swept size from which DEVICE's median is below
 HOST's by more than both cells' min-max spread, at that size and at every larger one (none: AUTO stays
 HOST).  The same A/B is run for PublicKey::verify at --signed items: hbh_hash_g2 + hbh_verify_sig_shares
-against hbh_verify_signatures forced to DEVICE."""
+against hbh_verify_signatures forced to DEVICE.
+
+--form lane | quad | both picks the device form(s) (hbh_engine_set_hash_form; default lane, the sweep of
+profiles/r14): with both, every alternation runs HOST, DEVICE-LANE and DEVICE-QUAD in turn, the three outputs
+must be equal bytes, and the Q form (hbh_engine_hash_g1_g2_bp) is measured the same way at --bp-sizes.  The
+sweep then supports two thresholds by the same rule of medians and spreads: HBH_AUTO_HASH_QUAD_MAX, the largest
+swept size up to which QUAD beats LANE at every swept size from the smallest, and HBH_AUTO_HASH_DEVICE_MIN
+over the better device form of each size."""
 import argparse
 import ctypes
 import json
@@ -53,44 +61,82 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def sweep_size(eng, n, reps):
+# a column of the sweep: (hbh_engine_set_hash_impl, hbh_engine_set_hash_form)
+FORMS = {"host": (_lib.HASH_HOST, _lib.HFORM_AUTO), "device": (_lib.HASH_DEVICE, _lib.HFORM_LANE),
+         "quad": (_lib.HASH_DEVICE, _lib.HFORM_QUAD)}
+COLUMNS = {"lane": ("host", "device"), "quad": ("host", "quad"), "both": ("host", "device", "quad")}
+
+
+def sweep_size(eng, n, reps, cols=("host", "device"), bp=False):
+    """one size: `cols` in turn, warm-up, outputs compared, `reps` alternations; bp: the Q form
+    (hbh_engine_hash_g1_g2_bp with one fixed U) instead of hbh_engine_hash_g2"""
     L = eng._l
     data, offs = messages(n, n)
     dbuf = (ctypes.c_uint8 * len(data)).from_buffer_copy(data)
     po = offs.ctypes.data_as(VP)
-    outs = {k: (ctypes.c_uint8 * (n * 192))() for k in ("host", "device")}
-    impl = {"host": _lib.HASH_HOST, "device": _lib.HASH_DEVICE}
+    outs = {k: (ctypes.c_uint8 * (n * 192))() for k in cols}
+    ub = (ctypes.c_uint8 * (96 * n)).from_buffer_copy(hoststage.g1_mul([G1_GEN], [0x1234567])[0] * n) if bp else None
 
     def call(form):
-        eng.set_hash_impl(impl[form])
-        _lib.check(L.hbh_engine_hash_g2(eng.handle, n, ctypes.cast(dbuf, VP), po, ctypes.cast(outs[form], VP)))
+        eng.set_hash_impl(FORMS[form][0])
+        eng.set_hash_form(FORMS[form][1])
+        if bp:
+            _lib.check(L.hbh_engine_hash_g1_g2_bp(eng.handle, n, ctypes.cast(ub, VP), ctypes.cast(dbuf, VP), po,
+                                                  ctypes.cast(outs[form], VP)))
+        else:
+            _lib.check(L.hbh_engine_hash_g2(eng.handle, n, ctypes.cast(dbuf, VP), po, ctypes.cast(outs[form], VP)))
 
-    for form in impl:
+    for form in cols:
         call(form)  # warm-up at this size
-    assert bytes(outs["host"]) == bytes(outs["device"]), "host and device hashes differ at n = %d" % n
-    t = {"host": [], "device": []}
+    for form in cols[1:]:
+        assert bytes(outs[cols[0]]) == bytes(outs[form]), "%s and %s hashes differ at n = %d" % (cols[0], form, n)
+    t = {form: [] for form in cols}
     for _ in range(reps):
-        for form in impl:
+        for form in cols:
             t[form].append(timed(lambda: call(form)))
-    kern = []
-    for _ in range(3):
-        eng.set_profiling(True)
-        call("device")
-        kern.append(eng.stage_time(_lib.STAGE_HASH)[0])
-        eng.set_profiling(False)
-    row = {"n": n, "host": cell(t["host"]), "device": cell(t["device"]), "device_kernel_ms": cell(kern)}
-    for form in impl:
+    row = {"n": n}
+    for form in cols:
+        row[form] = cell(t[form])
         row[form]["hashes_per_s"] = n / row[form]["median_ms"] * 1e3
+        if form == "host":
+            continue
+        kern = []
+        for _ in range(3):
+            eng.set_profiling(True)
+            call(form)
+            kern.append(eng.stage_time(_lib.STAGE_HASH)[0])
+            eng.set_profiling(False)
+        row[form + "_kernel_ms"] = cell(kern)
     return row
 
 
+def beats(a, b):
+    """cell a wins over cell b: b's median exceeds a's by more than the two min-max spreads together"""
+    return b["median_ms"] - a["median_ms"] > (a["max_ms"] - a["min_ms"]) + (b["max_ms"] - b["min_ms"])
+
+
+def best_device(row):
+    return min((f for f in ("device", "quad") if f in row), key=lambda f: row[f]["median_ms"])
+
+
 def wins(row):
-    h, d = row["host"], row["device"]
-    return h["median_ms"] - d["median_ms"] > (h["max_ms"] - h["min_ms"]) + (d["max_ms"] - d["min_ms"])
+    return beats(row[best_device(row)], row["host"])
+
+
+def quad_max(rows):
+    """largest swept size up to which QUAD beats LANE at every swept size from the smallest; 0: nowhere;
+    "all": everywhere"""
+    best = 0
+    for row in sorted(rows, key=lambda r: r["n"]):
+        if not beats(row["quad"], row["device"]):
+            return best
+        best = row["n"]
+    return "all"
 
 
 def threshold(rows):
-    """smallest swept size from which DEVICE wins at every larger swept size too; None: nowhere"""
+    """smallest swept size from which DEVICE (its better form at each size) wins at every larger swept
+    size too; None: nowhere"""
     best = None
     for row in sorted(rows, key=lambda r: -r["n"]):
         if not wins(row):
@@ -99,7 +145,7 @@ def threshold(rows):
     return best
 
 
-def signed_ab(eng, n, reps):
+def signed_ab(eng, n, reps, cols=("host", "device")):
     L = eng._l
     data, offs = messages(n, 7)
     msgs = [data[28 * i:28 * (i + 1)] for i in range(n)]
@@ -117,26 +163,32 @@ def signed_ab(eng, n, reps):
     po = offs.ctypes.data_as(VP)
     hb = (ctypes.c_uint8 * (192 * n))()
     idx = np.arange(n, dtype=np.uint32)
-    v = {k: (ctypes.c_uint8 * n)() for k in ("host", "device")}
+    v = {k: (ctypes.c_uint8 * n)() for k in cols}
 
     def host():
         _lib.check_host(L.hbh_hash_g2(n, ctypes.cast(dbuf, VP), po, ctypes.cast(hb, VP), 0))
         _lib.check(L.hbh_verify_sig_shares(eng.handle, n, ctypes.cast(pkb, VP), ctypes.cast(sgb, VP), ctypes.cast(hb, VP),
                                            n, idx.ctypes.data_as(VP), ctypes.cast(v["host"], VP)))
 
-    def device():
+    def device(form):
+        eng.set_hash_form(FORMS[form][1])
         _lib.check(L.hbh_verify_signatures(eng.handle, n, ctypes.cast(pkb, VP), ctypes.cast(sgb, VP), ctypes.cast(dbuf, VP),
-                                           po, ctypes.cast(v["device"], VP)))
+                                           po, ctypes.cast(v[form], VP)))
 
+    run = {form: (host if form == "host" else (lambda form=form: device(form))) for form in cols}
     eng.set_hash_impl(_lib.HASH_DEVICE)
-    host()
-    device()
-    assert bytes(v["host"]) == want and bytes(v["device"]) == want, "verdicts differ from the construction"
-    t = {"host": [], "device": []}
+    for form in cols:
+        run[form]()
+        assert bytes(v[form]) == want, "verdicts differ from the construction (%s)" % form
+    t = {form: [] for form in cols}
     for _ in range(reps):
-        t["host"].append(timed(host))
-        t["device"].append(timed(device))
-    return {"n": n, "hash_on_host_then_verify_signatures": cell(t["host"]), "verify_signed_device": cell(t["device"])}
+        for form in cols:
+            t[form].append(timed(run[form]))
+    name = {"host": "hash_on_host_then_verify_signatures", "device": "verify_signed_device", "quad": "verify_signed_quad"}
+    res = {"n": n}
+    for form in cols:
+        res[name[form]] = cell(t[form])
+    return res
 
 
 def fmt(c):
@@ -148,39 +200,74 @@ def main():
     ap.add_argument("--sizes", default=",".join(str(s) for s in SIZES))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--signed", type=int, default=10100, help="items of the verify_signed A/B (0: skip)")
+    ap.add_argument("--form", choices=sorted(COLUMNS), default="lane", help="device form(s) beside HOST")
+    ap.add_argument("--bp-sizes", default="10100,65536", help="sizes of the Q-form rows of --form both (empty: none)")
     ap.add_argument("--out", default=None, help="directory for hash_bench.json and hash_bench.md")
     a = ap.parse_args()
+    cols = COLUMNS[a.form]
+    dev_cols = cols[1:]
     eng = Engine(0)
-    res = {"host_threads": hoststage.host_threads(), "reps": a.reps, "message_bytes": 28, "rows": []}
+    res = {"host_threads": hoststage.host_threads(), "reps": a.reps, "message_bytes": 28, "form": a.form, "rows": []}
+
+    def show(tag, row):
+        print("%s n %6d  host %s" % (tag, row["n"], fmt(row["host"])) +
+              "".join("  %s %s  kernel %s ms" % (f, fmt(row[f]), fmt(row[f + "_kernel_ms"])) for f in dev_cols) +
+              "  " + ("DEVICE" if row["device_wins"] else "-") +
+              ("  QUAD" if row.get("quad_beats_lane") else ""), flush=True)
+
+    def one(n, bp):
+        row = sweep_size(eng, n, a.reps, cols, bp)
+        row["device_wins"] = wins(row)
+        if a.form == "both":
+            row["quad_beats_lane"] = beats(row["quad"], row["device"])
+            row["lane_beats_quad"] = beats(row["device"], row["quad"])
+        return row
+
     try:
         for n in [int(s) for s in a.sizes.split(",")]:
-            row = sweep_size(eng, n, a.reps)
-            row["device_wins"] = wins(row)
-            res["rows"].append(row)
-            print("n %6d  host %s  device %s  kernel %s ms  %s" % (n, fmt(row["host"]), fmt(row["device"]),
-                                                                    fmt(row["device_kernel_ms"]),
-                                                                    "DEVICE" if row["device_wins"] else "-"), flush=True)
+            res["rows"].append(one(n, False))
+            show("hash_g2", res["rows"][-1])
         res["auto_threshold"] = threshold(res["rows"])
         print("AUTO threshold supported by this sweep:", res["auto_threshold"], flush=True)
+        if a.form == "both":
+            res["quad_max"] = quad_max(res["rows"])
+            print("HBH_AUTO_HASH_QUAD_MAX supported by this sweep:", res["quad_max"], flush=True)
+            res["bp_rows"] = []
+            for n in [int(s) for s in a.bp_sizes.split(",") if s]:
+                res["bp_rows"].append(one(n, True))
+                show("Q form ", res["bp_rows"][-1])
         if a.signed:
-            res["verify_signed"] = s = signed_ab(eng, a.signed, a.reps)
-            print("verify_signed n %d  host hash + verify_signatures %s  device %s" %
-                  (s["n"], fmt(s["hash_on_host_then_verify_signatures"]), fmt(s["verify_signed_device"])), flush=True)
+            res["verify_signed"] = s = signed_ab(eng, a.signed, a.reps, cols)
+            print("verify_signed n %d  " % s["n"] + "  ".join("%s %s" % (k, fmt(c)) for k, c in s.items() if k != "n"),
+                  flush=True)
     finally:
         eng.set_hash_impl(_lib.HASH_AUTO)
+        eng.set_hash_form(_lib.HFORM_AUTO)
         eng.close()
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "hash_bench.json"), "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
+        label = {"device": "DEVICE-LANE" if a.form == "both" else "DEVICE", "quad": "DEVICE-QUAD"}
         with open(os.path.join(a.out, "hash_bench.md"), "w") as f:
-            f.write("| messages | HOST ms (min / median / max) | DEVICE ms (min / median / max) | HASH stage ms | "
-                    "HOST hashes/s | DEVICE hashes/s | DEVICE wins |\n|---|---|---|---|---|---|---|\n")
-            for r in res["rows"]:
-                f.write("| %d | %s | %s | %s | %.0f | %.0f | %s |\n" %
-                        (r["n"], fmt(r["host"]), fmt(r["device"]), fmt(r["device_kernel_ms"]), r["host"]["hashes_per_s"],
-                         r["device"]["hashes_per_s"], "yes" if r["device_wins"] else "no"))
+            for title, rows in (("hash_g2", res["rows"]), ("Q form (hash_g1_g2_bp)", res.get("bp_rows", []))):
+                if not rows:
+                    continue
+                f.write("%s, ms as min / median / max\n\n| messages | HOST |" % title +
+                        "".join(" %s | %s HASH stage |" % (label[c], label[c]) for c in dev_cols) +
+                        " HOST hashes/s |" + "".join(" %s hashes/s |" % label[c] for c in dev_cols) + " DEVICE wins |" +
+                        (" QUAD beats LANE |" if a.form == "both" else "") + "\n")
+                f.write("|---|---|" + "---|---|" * len(dev_cols) + "---|" + "---|" * len(dev_cols) + "---|" +
+                        ("---|" if a.form == "both" else "") + "\n")
+                for r in rows:
+                    f.write("| %d | %s |" % (r["n"], fmt(r["host"])) +
+                            "".join(" %s | %s |" % (fmt(r[c]), fmt(r[c + "_kernel_ms"])) for c in dev_cols) +
+                            " %.0f |" % r["host"]["hashes_per_s"] +
+                            "".join(" %.0f |" % r[c]["hashes_per_s"] for c in dev_cols) +
+                            " %s |" % ("yes" if r["device_wins"] else "no") +
+                            ((" %s |" % ("yes" if r["quad_beats_lane"] else "no")) if a.form == "both" else "") + "\n")
+                f.write("\n")
 
 
 if __name__ == "__main__":
