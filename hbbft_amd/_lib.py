@@ -78,6 +78,10 @@ SIGNATURES = [
     ("hbh_engine_hash_g1_g2_bp", _I, [_P, _SZ, _P, _P, _P, _P]),
     ("hbh_verify_ciphertexts_uv", _I, [_P, _SZ, _P, _P, _P, _P, _P]),
     ("hbh_engine_encrypt", _I, [_P, _SZ, _P, _I, _P, _P, _P, _P, _P, _P]),
+    # batched independent checks (opt-in): one final exponentiation per BATCH_GROUP items
+    ("hbh_verify_signatures_batched", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
+    ("hbh_verify_ciphertexts_uv_batched", _I, [_P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
+    ("hbh_dbg_pairing_product", _I, [_P, _SZ, _P, _P, _P]),
     ("hbh_engine_set_profiling", _I, [_P, _I]),
     ("hbh_engine_stage_time", _I, [_P, _I, _c.POINTER(_c.c_double), _c.POINTER(_I)]),
     # device-resident variants
@@ -133,6 +137,7 @@ GSUM_AUTO, GSUM_CHAIN, GSUM_BUCKET = 0, 1, 2  # HBH_GSUM_*
 AUTO_GSUM_G1_BUCKET_MIN, AUTO_GSUM_G2_BUCKET_MIN = 0, 0  # HBH_AUTO_GSUM_G*_BUCKET_MIN (0: never; profiles/r17)
 GSCALAR_INT128, GSCALAR_DIGITS = 0, 1  # HBH_GSCALAR_*: how a grouped call reads and draws its scalars
 GFORM_INT128, GFORM_X4, GFORM_X2 = 0, 1, 2  # HBH_GFORM_* (hbh_dbg_group_sums_form)
+BATCH_GROUP = 256  # HBH_BATCH_GROUP: items per final exponentiation of the batched independent checks
 GROUP_TILE = 128  # csrc/group_plan.hpp GROUP_TILE: items per tile of the grouped share checks' sums
 
 

@@ -2419,3 +2419,237 @@ int hbh_dbg_group_sums_form(hbh_engine* e, int form, size_t n, const uint8_t* g1
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- batched independent checks
+// Opt-in forms of hbh_verify_signatures / hbh_verify_ciphertexts_uv (include/hbbft_hip.h): the items share
+// no G2 point, so a group of HBH_BATCH_GROUP items is settled by ONE final exponentiation over the product
+// of its Miller values,
+//   prod_i f(r_i A_i, H_i) * f(-C, sum_i r_i B_i),   A = pk / U, B = sig / W, H = hash_g2 / Q_bp, C = g1 / G1K
+// (batch_plan.hpp plans the groups and tiles; k_scale_digits_g1 scales, the digit kernels of the grouped
+// checks sum, k_*_miller_prod multiplies a tile's Miller values, the wave kernel adds the closing pair
+// and runs the final exponentiation).  The items of a failed group and a single last item take the
+// per-item check on the hashes already in HBM, so every reported 0 is exact.
+#include "batch_plan.hpp"
+
+namespace {
+
+static_assert(HBH_BATCH_GROUP == BATCH_GROUP, "the ABI's group size is batch_plan.hpp's");
+
+struct BatchWidth {
+  hipError_t (*prod)(hipStream_t, int, int, const void*, const void*, int, int, uint32_t*);
+  uint32_t lanes;
+};
+
+// The Miller-product kernel of a call: a forced PAIR / QUAD / OCT is honoured, every other setting takes
+// AUTO's ladder read against the lane-kernel slots (two items per slot).  Call with e->mu held (inside the
+// EngineCall).
+BatchWidth batch_width(const hbh_engine* e, size_t slots) {
+  int impl = e->impl;
+  if (impl != HBH_IMPL_PAIR && impl != HBH_IMPL_QUAD && impl != HBH_IMPL_OCT)
+    impl = slots <= HBH_AUTO_OCT_MAX ? HBH_IMPL_OCT : slots <= HBH_AUTO_QUAD_MAX ? HBH_IMPL_QUAD : HBH_IMPL_PAIR;
+  if (impl == HBH_IMPL_OCT) return {hbl::oct_miller_prod, 8};
+  if (impl == HBH_IMPL_QUAD) return {hbl::quad_miller_prod, 4};
+  return {hbl::pair_miller_prod, 2};
+}
+
+// The tile products of the plan's groups over the device points d_p / d_q into value g * nf + t of
+// e->fval (t < tiles per group; the caller fills the values above).
+int launch_miller_prod(hbh_engine* e, hipStream_t s, const BatchPlan& B, const BatchWidth& w, const void* d_p,
+                       const void* d_q, uint32_t nf) {
+  const uint32_t tpg = batch_tiles_per_group(w.lanes);
+  HBH_CHECK(w.prod(s, (int)batch_miller_tiles(B, w.lanes), (int)B.nitems, d_p, d_q, (int)tpg, (int)nf, (uint32_t*)e->fval.p));
+  return HBH_OK;
+}
+
+// a: pk_i / U_i (G1); b: sig_i / W_i (G2); ct: Ciphertext::verify (the messages are V_i, hashed with U_i
+// to Q_bp) instead of PublicKey::verify
+int run_batched(hbh_engine* e, size_t n, const uint8_t* a, const uint8_t* b, bool ct, const uint8_t* data,
+                const size_t* offsets, const uint8_t* scalars, uint8_t* v, hbh_grouped_stats* stats) {
+  if (stats) *stats = hbh_grouped_stats{0, 0, 0, 0};
+  if (n == 0) return HBH_OK;
+  if (!a || !b || !v) return fail(HBH_ERR_ARG, "null pointer");
+  int rc = check_msgs(n, data, offsets);
+  if (rc) return rc;
+  std::vector<uint8_t> r;
+  rc = rlc_scalars(n, scalars, r);
+  if (rc) return rc;
+  BatchPlan B;
+  plan_batch(n, 2, B);
+  const size_t nc = B.ngroup;
+  bool device;
+  std::vector<uint8_t> g1k;
+  {  // where the hash runs is settled before the call opens, as in the unbatched calls (the host form hashes first)
+    std::lock_guard<std::mutex> lk(e->mu);
+    device = hash_on_device(e, n);
+    if (ct && e->g1k.empty()) {
+      e->g1k.resize(HBH_G1_BYTES);
+      rc = hbh_hash_bp_g1(e->g1k.data());
+      if (rc) {
+        e->g1k.clear();
+        return fail(rc, hbh_host_last_error());
+      }
+    }
+    if (ct) g1k = e->g1k;
+  }
+  const hbl::HashForm form = ct ? hbl::HASH_FORM_BP : hbl::HASH_FORM_FULL;
+  // every host array a queued copy reads lives to the end of the call
+  std::vector<uint8_t> h, seeds, state, fixed, gv(nc, 0), ga, gk, fv;
+  std::vector<uint32_t> packed, list;
+  if (!device) {
+    h.resize(n * HBH_G2_BYTES);
+    rc = ct ? hbh_hash_g1_g2_bp(n, a, data, offsets, h.data(), 0) : hbh_hash_g2(n, data, offsets, h.data(), 0);
+    if (rc) return fail(rc, hbh_host_last_error());
+  } else {
+    seeds.resize(n * 32);
+    state.resize(n);
+    hbh__hash_seeds(n, ct ? a : nullptr, data, offsets, seeds.data());
+  }
+  EngineCall call(e, nullptr, true);  // holds e->mu
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  const BatchWidth w = batch_width(e, batch_slots(B));  // under the call's lock, as hbh_dbg_pairing_product
+  // the hashes H_i / Q_i: in e->in_q1 for the group checks and the fallback alike
+  if (!device) {
+    HBH_CHECK(upload(s, e->in_q1, h.data(), n * HBH_G2_BYTES));
+  } else {
+    HBH_CHECK(upload(s, e->in_a, seeds.data(), n * 32));
+    HBH_CHECK(e->in_q1.ensure(n * HBH_G2_BYTES));
+    rc = launch_hash(e, s, n, (const uint8_t*)e->in_a.p, e->in_q1.p, form);
+    if (rc) return rc;
+    HBH_CHECK(download(s, state.data(), e->hash_state, n));
+    HBH_CHECK(hipStreamSynchronize(s));
+    const std::vector<uint32_t> left = hash_leftovers(state);
+    if (!left.empty()) {  // host-hashed, then patched into the table
+      fixed.resize(n * HBH_G2_BYTES);
+      (ct ? hbh__hash_g2_bp_seeds : hbh__hash_g2_seeds)(left.size(), left.data(), seeds.data(), fixed.data());
+      for (uint32_t i : left)
+        HBH_CHECK(h2d(s, (uint8_t*)e->in_q1.p + (size_t)i * HBH_G2_BYTES, fixed.data() + (size_t)i * HBH_G2_BYTES,
+                      HBH_G2_BYTES));
+    }
+  }
+  HBH_CHECK(upload(s, e->in_p1, a, n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_d, b, n * HBH_G2_BYTES));
+  if (nc) {
+    GroupDev d;
+    rc = upload_plan(e, s, B.groups, r, packed, d);  // the seeds in e->in_a are spent: the stream was synchronised
+    if (rc) return rc;
+    const uint32_t tpg = batch_tiles_per_group(w.lanes), nf = tpg + 1;
+    HBH_CHECK(e->work.ensure(2 * (size_t)d.ntile * hbl::group_tile_bytes(true)));
+    HBH_CHECK(e->in_p2.ensure(n * HBH_G1_BYTES));
+    HBH_CHECK(e->in_c.ensure(nc * HBH_G2_BYTES));
+    HBH_CHECK(e->fval.ensure((nc * nf + nc) * 576));
+    HBH_CHECK(e->out_x.ensure(nc * HBH_G1_BYTES));
+    HBH_CHECK(e->out_v.ensure(nc));
+    {
+      StageScope tm(e, s, HBH_STAGE_CURVE);
+      HBH_CHECK(hbl::scale_digits_g1(s, (int)B.nitems, e->in_p1.p, d.scalars, e->in_p2.p));
+      rc = launch_group_sums(e, s, true, n, e->in_d.p, d, 0, e->in_c.p, HBH_GFORM_X4);
+      if (rc) return rc;
+    }
+    if (ct) {  // the closing pair's G1K, one per group
+      gk.resize(nc * HBH_G1_BYTES);
+      for (size_t c = 0; c < nc; c++) std::memcpy(&gk[c * HBH_G1_BYTES], g1k.data(), HBH_G1_BYTES);
+      HBH_CHECK(upload(s, e->in_q2, gk.data(), gk.size()));
+    }
+    {
+      StageScope tm(e, s, HBH_STAGE_PAIRING);
+      rc = launch_miller_prod(e, s, B, w, e->in_p2.p, e->in_q1.p, nf);
+      if (rc) return rc;
+      // the closing pair f(-C, S_c) of every group: side 0 inactive (P = O), side 1 negated; its values
+      // land behind the tile values and move to slot tpg of their groups
+      uint32_t* fin = (uint32_t*)e->fval.p;
+      uint32_t* closing = fin + nc * nf * 144;
+      HBH_CHECK(hipMemsetAsync(e->out_x.p, 0, nc * HBH_G1_BYTES, s));
+      const hbl::PairSideDesc s0 = {e->out_x.p, e->in_c.p, nullptr, nullptr, nullptr, nc};
+      const hbl::PairSideDesc s1 = {ct ? e->in_q2.p : nullptr, e->in_c.p, nullptr, nullptr, nullptr, nc};
+      HBH_CHECK(hbl::wave_verify(s, (int)nc, s0, s1, hbl::WAVE_NEG_P2 | hbl::WAVE_MILLER_ONLY, nullptr, closing));
+      HBH_CHECK(hipMemcpy2DAsync(fin + tpg * 144, (size_t)nf * 576, closing, 576, 576, nc, hipMemcpyDeviceToDevice, s));
+      HBH_CHECK(hbl::wave_prod_fe(s, (int)nc, (int)nf, fin, (uint8_t*)e->out_v.p));
+    }
+    HBH_CHECK(download(s, gv.data(), e->out_v, nc));
+    HBH_CHECK(hipStreamSynchronize(s));
+  }
+  plan_batch_fallback(B, gv.data(), list);
+  if (stats) {
+    stats->groups = (uint32_t)nc;
+    for (uint8_t ok : gv) stats->groups_passed += ok ? 1 : 0;
+    stats->singles = (uint32_t)B.groups.singles.size();
+    stats->fallback_items = (uint32_t)list.size();
+  }
+  std::memset(v, 1, n);
+  const size_t m = list.size();
+  if (m) {
+    // the per-item check of the unbatched call on the listed items: P gathered, Q through the index map
+    // into the tables in HBM (n points each: no table is built for a map this sparse)
+    ga.resize(m * HBH_G1_BYTES);
+    fv.assign(m, 0);
+    for (size_t k = 0; k < m; k++) std::memcpy(&ga[k * HBH_G1_BYTES], a + (size_t)list[k] * HBH_G1_BYTES, HBH_G1_BYTES);
+    HBH_CHECK(upload(s, e->in_p2, ga.data(), ga.size()));
+    HBH_CHECK(upload(s, e->in_i1, list.data(), m * 4));
+    HBH_CHECK(e->out_v.ensure(m));
+    const uint32_t* d_idx = (const uint32_t*)e->in_i1.p;
+    if (ct) {  // e(G1K, W_i) == e(U_i, Q_i)
+      gk.resize(m * HBH_G1_BYTES);
+      for (size_t k = 0; k < m; k++) std::memcpy(&gk[k * HBH_G1_BYTES], g1k.data(), HBH_G1_BYTES);
+      HBH_CHECK(upload(s, e->in_q2, gk.data(), gk.size()));
+      rc = run_pairing_sides(e, s, m, {e->in_q2.p, e->in_d.p, nullptr, nullptr, d_idx, n},
+                             {e->in_p2.p, e->in_q1.p, nullptr, nullptr, d_idx, n}, Resident(), 1, (uint8_t*)e->out_v.p);
+    } else {  // e(pk_i, H_i) == e(g1, sig_i)
+      rc = run_pairing_sides(e, s, m, {e->in_p2.p, e->in_q1.p, nullptr, nullptr, d_idx, n},
+                             {nullptr, e->in_d.p, nullptr, nullptr, d_idx, n}, Resident(), 1, (uint8_t*)e->out_v.p);
+    }
+    if (rc) return rc;
+    HBH_CHECK(download(s, fv.data(), e->out_v, m));
+  }
+  rc = call.finish();
+  if (rc) return rc;
+  for (size_t k = 0; k < m; k++) v[list[k]] = fv[k];
+  return HBH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hbh_verify_signatures_batched(hbh_engine* e, size_t n, const uint8_t* pks, const uint8_t* sigs, const uint8_t* data,
+                                  const size_t* offsets, const uint8_t* scalars, uint8_t* v, hbh_grouped_stats* stats) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  return run_batched(e, n, pks, sigs, false, data, offsets, scalars, v, stats);
+}
+
+int hbh_verify_ciphertexts_uv_batched(hbh_engine* e, size_t n, const uint8_t* u, const uint8_t* data,
+                                      const size_t* offsets, const uint8_t* w, const uint8_t* scalars, uint8_t* v,
+                                      hbh_grouped_stats* stats) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  return run_batched(e, n, u, w, true, data, offsets, scalars, v, stats);
+}
+
+int hbh_dbg_pairing_product(hbh_engine* e, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out) {
+  if (!e) return fail(HBH_ERR_ARG, "null engine");
+  if (n == 0) return HBH_OK;
+  if (!p || !q || !out) return fail(HBH_ERR_ARG, "null pointer");
+  if (n > (size_t)1 << 26) return fail(HBH_ERR_ARG, "batch too large");
+  BatchPlan B;
+  plan_batch(n, 1, B);
+  const size_t nc = B.ngroup;
+  EngineCall call(e, nullptr, true);  // holds e->mu
+  if (call.rc) return call.rc;
+  hipStream_t s = call.s;
+  const BatchWidth w = batch_width(e, batch_slots(B));
+  const uint32_t tpg = batch_tiles_per_group(w.lanes);
+  HBH_CHECK(upload(s, e->in_p1, p, n * HBH_G1_BYTES));
+  HBH_CHECK(upload(s, e->in_q1, q, n * HBH_G2_BYTES));
+  HBH_CHECK(e->fval.ensure(nc * tpg * 576));
+  HBH_CHECK(e->out_v.ensure(nc * 576));
+  {
+    StageScope tm(e, s, HBH_STAGE_PAIRING);
+    const int rc = launch_miller_prod(e, s, B, w, e->in_p1.p, e->in_q1.p, tpg);
+    if (rc) return rc;
+    HBH_CHECK(hbl::wave_prod_fe(s, (int)nc, (int)tpg, (const uint32_t*)e->fval.p, nullptr, (uint32_t*)e->out_v.p,
+                                hbl::WAVE_CONJ_VALUE));
+  }
+  HBH_CHECK(download(s, out, e->out_v, nc * 576));
+  return call.finish();
+}
+
+}  // extern "C"

@@ -83,14 +83,15 @@ hipError_t wave_miller_tree(hipStream_t s, int ngroup, int nw, const PairSideDes
   return hipGetLastError();
 }
 
-hipError_t wave_prod_fe(hipStream_t s, int n, int nf, const uint32_t* fin, uint8_t* verdict) {
+hipError_t wave_prod_fe(hipStream_t s, int n, int nf, const uint32_t* fin, uint8_t* verdict, uint32_t* value_out,
+                        int value_flags) {
   if (n <= 0) return hipSuccess;
   if (nf <= 0 || !fin) return hipErrorInvalidValue;
   hbs::WaveArgs a = {};
   a.n = n;
-  a.flags = 0;
+  a.flags = value_flags & WAVE_CONJ_VALUE;  // product mode reads no other flag
   a.verdict = verdict;
-  a.value_out = nullptr;
+  a.value_out = value_out;
   a.fin = fin;
   a.nf = nf;
   hipLaunchKernelGGL(hbs::k_wave, dim3((unsigned)n), dim3(64), wave_lds_bytes(), s, a);

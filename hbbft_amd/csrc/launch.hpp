@@ -51,6 +51,21 @@ hipError_t quad_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairS
 hipError_t oct_verify(hipStream_t s, int n, const PairSideDesc& s1, const PairSideDesc& s2, int flags,
                       uint8_t* verdict, uint32_t* value_out);
 
+// --------------------------------------------------------------- Miller products (k_mprod_pair/quad/oct.hip)
+// The lane kernels of the batched checks (pair_side.hpp lane_miller_prod): the same Miller loop with two
+// CONSECUTIVE ITEMS (p[i], q[i]) as a slot's two sides, no final exponentiation.  Tile b (one workgroup)
+// multiplies the Miller values of the items [b T, min(n, (b + 1) T)), T = 256, 128, 64 items on lane pairs,
+// quads, octos, and writes the product (144 canonical words, w-basis: wave_prod_fe's input) as value
+// (b / tpg) * nf + b % tpg of out: with tpg = 256 / T tiles per group and nf >= tpg, a group's tile
+// values are consecutive and nf - tpg values per group are left to the caller.  An item with P = O or
+// Q = O contributes 1.
+hipError_t pair_miller_prod(hipStream_t s, int ntile, int n, const void* p, const void* q, int tpg, int nf,
+                            uint32_t* out);
+hipError_t quad_miller_prod(hipStream_t s, int ntile, int n, const void* p, const void* q, int tpg, int nf,
+                            uint32_t* out);
+hipError_t oct_miller_prod(hipStream_t s, int ntile, int n, const void* p, const void* q, int tpg, int nf,
+                           uint32_t* out);
+
 // --------------------------------------------------------------- wave-per-check pairing (k_wave.hip)
 // The same verdicts / values as pair_verify with one 64-lane workgroup per check (the latency
 // kernel: a check's Fp2 products run on 32 lane pairs side by side).  TABLE sides read oct_prep
@@ -68,7 +83,10 @@ constexpr int WAVE_JAC_P = 8;
 // flags bit 4 (WAVE_ONE_SIDE, with WAVE_JAC_P): one pair per check, side 0 only (side 1 is not read):
 // the homogeneous-walk Miller program (two stages per step instead of three)
 constexpr int WAVE_ONE_SIDE = 16;
-hipError_t wave_prod_fe(hipStream_t s, int n, int nf, const uint32_t* fin, uint8_t* verdict);
+// value_out (may be null): FE(prod) as 144 canonical words per check in pair_verify's value format,
+// conjugated under WAVE_CONJ_VALUE (bit 1 of value_flags).
+hipError_t wave_prod_fe(hipStream_t s, int n, int nf, const uint32_t* fin, uint8_t* verdict,
+                        uint32_t* value_out = nullptr, int value_flags = 0);
 // wave_verify's Miller-only mode with the product and the final exponentiation in the same launch:
 // the n = ngroup * nw checks form ngroup groups of nw consecutive checks; within a group the Miller
 // values are multiplied up a binary tree (the later-arriving wave of each sibling pair multiplies,
@@ -183,6 +201,9 @@ hipError_t group_digits_g1(hipStream_t s, int form, int ntile, int n, int max_le
 hipError_t group_digits_g2(hipStream_t s, int form, int ntile, int n, int max_len, const void* pts,
                            const uint32_t* scalars, const uint32_t* perm, const uint32_t* tile_off,
                            const uint32_t* tile_len, void* tile_sums);
+// scale_digits_g1: out[i] = r_i pts[i] (affine ABI words, all-zero for O), r_i the X4 digits of scalars
+// (4 words per item): the per-item G1 side of the batched checks, one 96-step joint chain per lane.
+hipError_t scale_digits_g1(hipStream_t s, int n, const void* pts, const uint32_t* scalars, void* out);
 hipError_t group_join_g1(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 hipError_t group_join_g2(hipStream_t s, int ngroup, const uint32_t* ctile, const void* tile_sums, void* out);
 

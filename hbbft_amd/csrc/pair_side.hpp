@@ -282,10 +282,105 @@ HP_D void lane_verify(const PairArgs& a, uint32_t* stash) {
   if (G::leader() && a.verdict) a.verdict[i] = one ? 1 : 0;
 }
 
+// ---------------------------------------------------------------- the Miller product
+// The batched checks' lane kernel (hbh_verify_signatures_batched, hbh_verify_ciphertexts_uv_batched,
+// hbh_dbg_pairing_product): no final exponentiation here.  A group of G::LANES lanes takes TWO
+// CONSECUTIVE ITEMS (P_i, Q_i), (P_i+1, Q_i+1) as the two sides of lane_verify's loop (both WALK, both P
+// read), so a 256-thread workgroup -- a tile -- holds T = 2 * 256 / G::LANES items; the Miller values of
+// the tile's 256 / G::LANES slots are multiplied up a binary tree through the LDS stash, and the tile's
+// product is written as 144 canonical words in the layout wave_prod_fe reads (k_wave.hpp: the w-basis,
+// component k at word 24 k; tower component c0.cj is k = 2 j, c1.cj is k = 2 j + 1).  An item past n, or
+// with P = O or Q = O, is an inactive pair and contributes 1 (side_init's act); every lane stays to the
+// last barrier.  The value is the raw product of f_{|x|,Q}(P), times subfield factors that the final
+// exponentiation removes: FE(conj(value)) = prod e(P_i, Q_i)^3.
+struct MillerProdArgs {
+  int n;              // items; tile b takes the items [b T, min(n, (b + 1) T))
+  const uint32_t* p;  // G1 points, 24 words per item
+  const uint32_t* q;  // G2 points, 48 words per item
+  int tpg, nf;        // tile b is value (b / tpg) * nf + b % tpg of out (tpg tiles per group, nf values per group)
+  uint32_t* out;      // 144 words per value
+};
+
+template <class G>
+HP_D void lane_miller_prod(const MillerProdArgs& a, uint32_t* stash) {
+  constexpr int SLOTS = 256 / G::LANES;
+  const int slot = (int)threadIdx.x / G::LANES;
+  const int i0 = 2 * ((int)blockIdx.x * SLOTS + slot), i1 = i0 + 1, last = a.n - 1;
+  const PairSide sd = {a.p, a.q, nullptr, nullptr, nullptr, (uint32_t)a.n};
+  SideStateT<typename G::Walk> A, B;
+  // an item past n reads item n - 1 and is masked out: its lanes walk along to the barriers
+  side_init<true, false>(sd, i0 < last ? i0 : last, false, A);
+  side_init<true, false>(sd, i1 < last ? i1 : last, false, B);
+  A.act = A.act && i0 < a.n;
+  B.act = B.act && i1 < a.n;
+  uint32_t* col = stash + threadIdx.x;
+  const typename G::template Park<true, true, 0> pk(col);
+  pk.init(A, B);
+  H12 f = h12_one();
+  int step = 0;
+#pragma unroll 1
+  for (int b = 62; b >= 0; b--) {
+    if (b != 62) f = h12_sqr<G>(f);
+    {
+      HLine la, lb;
+      G::template lines_at_p<false, false, false>([&]() HS_LAMBDA { return side_raw<G, true, true, 0>(sd, A, step, pk); },
+                                                  [&]() HS_LAMBDA { return side_raw<G, true, true, 1>(sd, B, step, pk); },
+                                                  A, B, false, la, lb, pk);
+      constexpr bool FL = G::template first_line<true, true>();
+      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4, FL && b == 62);
+    }
+    step++;
+    if ((hb::X_ABS >> b) & 1) {
+      HLine la, lb;
+      G::template lines_at_p<false, false, false>([&]() HS_LAMBDA { return side_raw<G, true, false, 0>(sd, A, step, pk); },
+                                                  [&]() HS_LAMBDA { return side_raw<G, true, false, 1>(sd, B, step, pk); },
+                                                  A, B, false, la, lb, pk);
+      f = h12_mul_lines<G>(f, la.c0, la.c1, la.c4, lb.c0, lb.c1, lb.c4);
+      step++;
+    }
+  }
+  // The tree: a slot's value waits in its lanes' columns (reduced to [0, 2p) by stash_fp: h12_mul's
+  // input bound).  At level L the slots that are multiples of 2^(L+1) multiply in slot + 2^L, whose
+  // columns nobody writes at this level, so one barrier per level orders writes and reads.  The lanes
+  // of a slot branch together (the cross-lane moves of a product stay inside the slot).
+  stash12(col, f);
+  __syncthreads();
+#pragma unroll 1
+  for (int L = 0; (1 << L) < SLOTS; L++) {
+    if ((slot & ((2 << L) - 1)) == 0) {
+      const H12 g = unstash12(col + (G::LANES << L));
+      const H12 m = h12_mul<G>(unstash12(col), g);
+      stash12(col, m);
+    }
+    __syncthreads();
+  }
+  if (slot == 0 && G::value_writer()) {
+    const H12 e = unstash12(col);
+    uint32_t* o = a.out + ((size_t)(blockIdx.x / a.tpg) * a.nf + blockIdx.x % a.tpg) * 144 + (lp_even() ? 0 : 12);
+    fp_to_words(e.c0.c0, o + 0);
+    fp_to_words(e.c1.c0, o + 24);
+    fp_to_words(e.c0.c1, o + 48);
+    fp_to_words(e.c1.c1, o + 72);
+    fp_to_words(e.c0.c2, o + 96);
+    fp_to_words(e.c1.c2, o + 120);
+  }
+}
+
 }  // namespace hbs
 
 // ---------------------------------------------------------------- launching
 namespace hbl {
+
+// the Miller-product kernel K (a width's k_*_miller_prod) over ntile tiles of 2 * 256 / LANES items
+template <class K>
+hipError_t miller_prod_launch(K kernel, hipStream_t s, int ntile, int n, const void* p, const void* q, int tpg, int nf,
+                              uint32_t* out) {
+  if (ntile <= 0) return hipSuccess;
+  if (n <= 0 || tpg <= 0 || nf < tpg || !p || !q || !out) return hipErrorInvalidValue;
+  const hbs::MillerProdArgs a = {n, (const uint32_t*)p, (const uint32_t*)q, tpg, nf, out};
+  hipLaunchKernelGGL(kernel, dim3((unsigned)ntile), dim3(256), (size_t)hbs::STASH_WORDS * 256 * 4, s, a);
+  return hipGetLastError();
+}
 
 inline hbs::PairArgs pair_args(int n, const PairSideDesc& d1, const PairSideDesc& d2, int flags, uint8_t* verdict,
                                uint32_t* value_out) {

@@ -61,11 +61,16 @@ class DhbKeyGen:
     (KeyGenState::public_keys, the validator set being generated; None when no key generation)."""
 
     def __init__(self, engine, era, our_id, secret_key, public_keys, key_gen=None, candidate_keys=None,
-                 is_validator=True, threads=0, device_hash=False):
+                 is_validator=True, threads=0, device_hash=False, batched=False):
+        if batched and not device_hash:
+            raise ValueError("batched is a form of the device_hash check: it needs device_hash=True")
         self.engine, self.era, self.our_id = engine, era, our_id
         self.secret_key = secret_key
         self.public_keys = dict(public_keys)
         self.device_hash = device_hash  # batch checks hash their messages in the engine (verify_signed)
+        # with device_hash: verify_signed_batched, one final exponentiation per 256 checks (scalars drawn
+        # by the engine, exact verdicts for failed groups); same outcomes and faults.  Default: off.
+        self.batched = bool(batched)
         # key_gen is made by the caller: SyncKeyGen.new(..., device_hash=True) gives its Ciphertext::verify
         # and encryption batches the same treatment (this flag does not reach into it)
         self.key_gen = key_gen
@@ -114,7 +119,10 @@ class DhbKeyGen:
         ok = [False] * len(items)
         if pks:
             if self.device_hash:  # one hash per check: a message checked under two keys is hashed twice
-                v = self.engine.verify_signed(pks, sigs, [msgs[k] for k in hidx])
+                if self.batched:
+                    v = self.engine.verify_signed_batched(pks, sigs, [msgs[k] for k in hidx])[0]
+                else:
+                    v = self.engine.verify_signed(pks, sigs, [msgs[k] for k in hidx])
             else:
                 v = self.engine.verify_sig_shares(pks, sigs, hs, hidx)
             self.calls += 1
@@ -273,11 +281,15 @@ class VoteCounter:
     {node_id: ABI G1} (NetworkInfo::public_key); num_faulty: f.  ``calls`` / ``checks`` count the
     engine calls and the signatures they verified."""
 
-    def __init__(self, engine, era, our_id, secret_key, public_keys, num_faulty, threads=0, device_hash=False):
+    def __init__(self, engine, era, our_id, secret_key, public_keys, num_faulty, threads=0, device_hash=False,
+                 batched=False):
+        if batched and not device_hash:
+            raise ValueError("batched is a form of the device_hash check: it needs device_hash=True")
         self.engine, self.era, self.our_id = engine, era, our_id
         self.secret_key = secret_key
         self.public_keys = dict(public_keys)
         self.device_hash = device_hash  # validate() hashes the votes in the engine (verify_signed)
+        self.batched = bool(batched)    # ... through verify_signed_batched (one final exponentiation per 256)
         self.num_faulty = num_faulty
         self.threads = threads
         self.pending = {}    # voter -> SignedVote
@@ -301,7 +313,9 @@ class VoteCounter:
         if idx:
             msgs = vote_bytes([signed_votes[k].vote for k in idx])
             pks, sigs = [self.public_keys[signed_votes[k].voter] for k in idx], [signed_votes[k].sig for k in idx]
-            if self.device_hash:
+            if self.device_hash and self.batched:
+                v = self.engine.verify_signed_batched(pks, sigs, msgs)[0]
+            elif self.device_hash:
                 v = self.engine.verify_signed(pks, sigs, msgs)
             else:
                 v = self.engine.verify_signatures(pks, sigs, hoststage.hash_g2(msgs, threads=self.threads))

@@ -339,6 +339,58 @@ class Engine:
                                                     ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)))
         return bytes(out)[:n], GroupedStats(st.groups, st.groups_passed, st.singles, st.fallback_items)
 
+    # ------------------------------------------------------------ batched independent checks (opt-in)
+    def _batched(self, ab, bb, msgs, scalars):
+        from .hoststage import _concat
+        n = len(ab) // G1_BYTES
+        if len(bb) // G2_BYTES != n or len(msgs) != n:
+            raise ValueError("points / messages length mismatch")
+        data, offs = _concat(msgs)
+        rk, pr = self._rlc_scalars(scalars, n)
+        out = (ctypes.c_uint8 * max(n, 1))()
+        st = _lib.GroupedStats()
+        keep = [buf(ab or b"\0"), buf(bb or b"\0"), buf(data or b"\0")]
+        return n, keep, offs, pr, rk, out, st
+
+    def verify_signed_batched(self, pks, sigs, msgs, scalars=None):
+        """verify_signed with one final exponentiation per BATCH_GROUP = 256 items
+        (hbh_verify_signatures_batched): prod e(r_i pk_i, H_i) e(-g1, sum r_i sig_i) == 1 per group, and the
+        per-item check for the items of a failed group and a single last item: (verdicts, GroupedStats).
+        ``scalars`` None: the engine draws them; given scalars are 16 bytes per item read as X4 digits
+        (``digit_scalar(GFORM_X4, ...)`` packs them) and used as they are -- the caller's responsibility."""
+        n, keep, offs, pr, rk, out, st = self._batched(_join(pks, G1_BYTES), _join(sigs, G2_BYTES), msgs, scalars)
+        check(self._l.hbh_verify_signatures_batched(self._h, n, keep[0][1], keep[1][1], keep[2][1],
+                                                    offs.ctypes.data_as(ctypes.c_void_p), pr,
+                                                    ctypes.cast(out, ctypes.c_void_p),
+                                                    ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)))
+        return bytes(out)[:n], GroupedStats(st.groups, st.groups_passed, st.singles, st.fallback_items)
+
+    def verify_ciphertexts_uv_batched(self, us, vs, ws, scalars=None):
+        """verify_ciphertexts_uv with one final exponentiation per BATCH_GROUP = 256 ciphertexts
+        (hbh_verify_ciphertexts_uv_batched): prod e(r_i U_i, Q_i) e(-G1K, sum r_i W_i) == 1 per group:
+        (verdicts, GroupedStats); scalars as verify_signed_batched."""
+        n, keep, offs, pr, rk, out, st = self._batched(_join(us, G1_BYTES), _join(ws, G2_BYTES), vs, scalars)
+        check(self._l.hbh_verify_ciphertexts_uv_batched(self._h, n, keep[0][1], keep[2][1],
+                                                        offs.ctypes.data_as(ctypes.c_void_p), keep[1][1], pr,
+                                                        ctypes.cast(out, ctypes.c_void_p),
+                                                        ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)))
+        return bytes(out)[:n], GroupedStats(st.groups, st.groups_passed, st.singles, st.fallback_items)
+
+    def dbg_pairing_product(self, p, q):
+        """(prod of e(p[i], q[i]) over each group of BATCH_GROUP = 256 consecutive items)^3, one value per
+        group in dbg_pairing's format (hbh_dbg_pairing_product): the Miller-product kernel and the product
+        mode of the wave kernel, without the protocol around them.  Tests only."""
+        pb, qb = _join(p, G1_BYTES), _join(q, G2_BYTES)
+        n = len(pb) // G1_BYTES
+        if len(qb) // G2_BYTES != n:
+            raise ValueError("p / q length mismatch")
+        ng = (n + _lib.BATCH_GROUP - 1) // _lib.BATCH_GROUP
+        out = (ctypes.c_uint8 * max(ng * 576, 1))()
+        keep = [buf(x or b"\0") for x in (pb, qb)]
+        check(self._l.hbh_dbg_pairing_product(self._h, n, keep[0][1], keep[1][1], ctypes.cast(out, ctypes.c_void_p)))
+        raw = bytes(out)[: ng * 576]
+        return [raw[i * 576:(i + 1) * 576] for i in range(ng)]
+
     def dbg_group_sums(self, g1_pts, g2_pts, ngroups, group_idx, scalars):
         """The sums behind the grouped checks (hbh_dbg_group_sums): ([sum of r_i g1_pts[i] over the
         items of group k], [the same for g2_pts]) for k < ngroups; a point list may be None (its

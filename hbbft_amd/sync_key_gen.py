@@ -209,15 +209,19 @@ class PublicKeySet:
 
 
 # ------------------------------------------------------------------ crypto batches
-def _decrypt_batch(engine, sec_key, cts, threads=0, device_hash=False):
+def _decrypt_batch(engine, sec_key, cts, threads=0, device_hash=False, batched=False):
     """SecretKey::decrypt for a list of ciphertexts: None where Ciphertext::verify fails
     (sync_key_gen.rs:503-506, 535-538).  device_hash: Ciphertext::verify from (U, V, W) in one engine
-    call (hbh_verify_ciphertexts_uv), which hashes large batches on the device; the same verdicts."""
+    call (hbh_verify_ciphertexts_uv), which hashes large batches on the device; the same verdicts.
+    batched (with device_hash): that call's batched form (hbh_verify_ciphertexts_uv_batched: one final
+    exponentiation per 256 ciphertexts, scalars drawn by the engine, exact verdicts for failed groups)."""
     if not cts:
         return []
     # Ciphertext::verify in its Q form (hbh_hash_g1_g2_bp): the same verdicts without the final
     # G2 scalar multiplication of each hash
-    if device_hash:
+    if device_hash and batched:
+        ok = engine.verify_ciphertexts_uv_batched([c.u for c in cts], [c.v for c in cts], [c.w for c in cts])[0]
+    elif device_hash:
         ok = engine.verify_ciphertexts_uv([c.u for c in cts], [c.v for c in cts], [c.w for c in cts])
     else:
         qbp = hoststage.hash_g1_g2_bp([c.u for c in cts], [c.v for c in cts], threads)
@@ -244,11 +248,15 @@ def _encrypt_batch(pks, payloads, rng, threads=0, engine=None):
 
 # ------------------------------------------------------------------ SyncKeyGen
 class SyncKeyGen:
-    def __init__(self, our_id, sec_key, pub_keys, threshold, engine, threads=0, device_hash=False):
+    def __init__(self, our_id, sec_key, pub_keys, threshold, engine, threads=0, device_hash=False, batched=False):
         """sec_key: this node's encryption secret key (Fr int); pub_keys: {node_id: G1 ABI}.
         device_hash: take hash_g1_g2 of the public (U, V) of every ciphertext this instance checks or
         makes through the engine (verify_ciphertexts_uv, Engine.encrypt), which hashes large batches on
-        the device (Engine.set_hash_impl); same messages, outcomes and keys."""
+        the device (Engine.set_hash_impl); same messages, outcomes and keys.
+        batched (needs device_hash; a ValueError without it): Ciphertext::verify through
+        verify_ciphertexts_uv_batched; same outcomes and fault reports.  Default: off."""
+        if batched and not device_hash:
+            raise ValueError("batched is a form of the device_hash check: it needs device_hash=True")
         self.our_id = our_id
         self.sec_key = sec_key
         self.pub_keys = dict(sorted(pub_keys.items()))
@@ -259,6 +267,7 @@ class SyncKeyGen:
         self.engine = engine
         self.threads = threads
         self.device_hash = bool(device_hash)
+        self.batched = bool(batched)
         self._sets = {}  # degree -> CommitSet: every Part's commitment uploaded to HBM once
 
     def _commit_set(self, degree):
@@ -268,12 +277,12 @@ class SyncKeyGen:
         return cs
 
     @classmethod
-    def new(cls, our_id, sec_key, pub_keys, threshold, engine, rng=None, threads=0, device_hash=False):
+    def new(cls, our_id, sec_key, pub_keys, threshold, engine, rng=None, threads=0, device_hash=False, batched=False):
         """SyncKeyGen::new (sync_key_gen.rs:323-357): the instance and our Part (None for an
         observer).  BivarPoly::random(threshold), commitment on the GPU, one encrypted row per
         node on the host."""
         rng = rng or random.SystemRandom()
-        kg = cls(our_id, sec_key, pub_keys, threshold, engine, threads, device_hash)
+        kg = cls(our_id, sec_key, pub_keys, threshold, engine, threads, device_hash, batched)
         if kg.our_idx is None:
             return kg, None
         t = threshold
@@ -351,7 +360,7 @@ class SyncKeyGen:
                 for j, r in zip(js, got):
                     commit_rows[j] = r
             plain = _decrypt_batch(self.engine, self.sec_key, [p.rows[self.our_idx] for _, p, _ in new], self.threads,
-                                   self.device_hash)
+                                   self.device_hash, self.batched)
             polys = [de_row(b) if b is not None else None for b in plain]
             # Poly::commitment() only where the lengths agree: a row of another length can never
             # equal the commitment row (Commitment's derived PartialEq compares the vectors)
@@ -448,7 +457,7 @@ class SyncKeyGen:
         verdict = {}
         if new and self.our_idx is not None:
             plain = _decrypt_batch(self.engine, self.sec_key, [a.values[self.our_idx] for _, a, _ in new], self.threads,
-                                   self.device_hash)
+                                   self.device_hash, self.batched)
             vals = [de_val(b) if b is not None else None for b in plain]
             chk = [j for j, v in enumerate(vals) if v is not None]
             okmap = {}

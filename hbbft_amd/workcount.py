@@ -276,3 +276,54 @@ def group_sum_critical_path(kind, impl, L):
     _, (pdbl, padd) = _gsum_tail(kind)
     slots = L if kind == "g1" else 2 * L + L * GSUM_D2_RATE   # window 0's wave takes the psi^2(P) terms
     return slots * madd + (3 * add + dbl) + pdbl * dbl + padd * add
+
+
+# ---------------------------------------------------------------------------- batched independent checks
+# hbh_verify_signatures_batched / hbh_verify_ciphertexts_uv_batched against the per-item check, per ITEM,
+# in Fp products from the weights above.  An op model only: what the calls measure is profiles/r25.
+BATCH_GROUP = 256                         # HBH_BATCH_GROUP: items per final exponentiation
+BATCH_TILE_ITEMS = {2: 256, 4: 128, 8: 64}   # items per workgroup of the Miller-product kernel, by lanes per slot
+PER_ITEM_CHECK = MILLER_2PAIR + 2 * G2_WALK + FINAL_EXP   # the unbatched call: both sides walked
+# an item is ONE side of a two-item slot: half a 2-pair Miller loop and one walk
+BATCH_MILLER_ITEM = MILLER_2PAIR / 2 + G2_WALK
+# r_i P_i: the X4 joint chain of 96 steps with one lane per item -- under SIMT every lane pays every
+# addition --, the two scaled abscissae of its table, and the affine output (an inversion, Z^-2, Z^-3, x, y)
+BATCH_G1_CHAIN = 96 * (G1_DBL[0] + G1_MADD[0]) + 2 + (FP_INV + 5)
+# the item's share of sum r_i B_i in G2: two joint chains of 32 steps (every lane pays every addition), their
+# tables, the second chain added into the first, and one addition of the tile's tree
+BATCH_G2_SUM_ITEM = 2 * (32 * (G2_DBL[0] + G2_MADD[0]) + 4) + 2 * G2_ADD[0]
+# per group: the closing pair (one Miller-only wave check), one final exponentiation
+BATCH_CLOSING_GROUP = MILLER_1PAIR + G2_WALK
+
+
+def batch_tree_item(lanes, executed=True):
+    """The Fp12 products of the product tree, per item.  Issued: a tile of T items multiplies T / 2 slot
+    values with T / 2 - 1 products, and the wave kernel's product mode multiplies the group's tiles and the
+    closing value -- 128 products per 256 items at every width.  Executed: a wave runs a level's product
+    whenever one of its slots multiplies, so every slot pays log2(T / 2) products (the default)."""
+    slots = BATCH_TILE_ITEMS[lanes] // 2
+    tpg = BATCH_GROUP // BATCH_TILE_ITEMS[lanes]
+    if executed:
+        return ((slots.bit_length() - 1) * F12_MUL) / 2 + tpg * F12_MUL / BATCH_GROUP
+    return ((slots - 1) * tpg + tpg) * F12_MUL / BATCH_GROUP
+
+
+def batched_model(lanes=2, executed=True):
+    """Per-item entries of the batched check with no failed group: {entry: Fp products}."""
+    return {
+        "miller_product": BATCH_MILLER_ITEM,
+        "tree": batch_tree_item(lanes, executed),
+        "g1_chain": BATCH_G1_CHAIN,
+        "g2_sum": BATCH_G2_SUM_ITEM,
+        "closing_pair": BATCH_CLOSING_GROUP / BATCH_GROUP,
+        "final_exp": FINAL_EXP / BATCH_GROUP,
+    }
+
+
+def batched_model_ratio(lanes=2, executed=True, pairing_only=False):
+    """Model cost of the batched check over the per-item check (no failed group; a failed group pays
+    both).  pairing_only: HBH_STAGE_PAIRING's entries against the same per-item check."""
+    m = batched_model(lanes, executed)
+    if pairing_only:
+        m = {k: v for k, v in m.items() if k not in ("g1_chain", "g2_sum")}
+    return sum(m.values()) / PER_ITEM_CHECK

@@ -490,6 +490,77 @@ int hbh_verify_ciphertexts_uv(hbh_engine* eng, size_t n, const uint8_t* u, const
 int hbh_engine_encrypt(hbh_engine* eng, size_t n, const uint8_t* pks, int pk_per_item, const uint8_t* data,
                        const size_t* offsets, const uint8_t* nonces, uint8_t* u_out, uint8_t* v_out, uint8_t* w_out);
 
+/* ---------------------------------------------------------------- batched independent checks (opt-in)
+ * hbh_verify_signatures / hbh_verify_ciphertexts_uv with ONE final exponentiation per group of
+ * HBH_BATCH_GROUP items.  These items share no G2 point, so the grouped share checks above do not apply;
+ * the random combination is taken over whole pairings instead:
+ *   signatures:   prod_i e(r_i pk_i, H_i) * e(-g1,  sum_i r_i sig_i) == 1
+ *   ciphertexts:  prod_i e(r_i U_i,  Q_i) * e(-G1K, sum_i r_i W_i)   == 1      (Q_i = Q_bp(U_i, V_i))
+ * Group g holds the items [256 g, min(n, 256 g + 256)) in call order; a last group of one item is a
+ * single and takes the per-item check.  Per group: r_i P_i per item (k_rlc_digits.hip k_scale_digits_g1),
+ * the G2 sum (the digit kernels of the grouped share checks), the Miller values of the items multiplied up
+ * a tree inside the lane kernel (pair_side.hpp lane_miller_prod: two items per slot, no final
+ * exponentiation; 1, 2 or 4 tiles per group on lane pairs, quads, octos), the closing pair as one
+ * Miller-only wave check, and one product + final exponentiation (the wave kernel's product mode).
+ * A group whose check holds reports every member valid; the items of a group whose check fails, and the
+ * single, are re-checked item by item by the unbatched pairing path, so a verdict of 0 is always exact.
+ * A verdict of 1 from a passed group is the reference's verdict except with probability at most
+ * 1 / (2^128 - 1) per group holding an invalid item -- PROVIDED the points are in the prime-order
+ * subgroups (the ABI's contract) and the scalars are uniform, independent of the inputs, and unknown to
+ * whoever chose the items.
+ *   Scalars: 16 bytes per item, ALWAYS read as X4 digits (four LE u32 a0..a3, r_i = a0 + a1 |x| + a2 |x|^2 +
+ *     a3 |x|^3: the layout hbh_verify_sig_shares_grouped reads under HBH_GSCALAR_DIGITS, with the same
+ *     uniqueness argument), the same residue on the G1 side and in the G2 sum.
+ *     hbh_engine_set_group_scalar_form and hbh_engine_set_group_sum_impl do not govern these calls.
+ *     scalars == NULL: the engine draws them from the OS (getrandom) and replaces an all-zero draw: the form
+ *     the bound is stated for.  scalars != NULL: USED AS GIVEN (an all-zero tuple is HBH_ERR_ARG); the bound
+ *     then holds only if the caller's scalars meet the conditions above.
+ *   Hashing: exactly as in the unbatched calls (hbh_engine_set_hash_impl / _hash_form, the Q form for
+ *     ciphertexts, leftovers of the sampler rounds patched in from the host stage).  The hashes computed
+ *     for the call serve the group checks AND the fallback: no item is hashed twice, on the device form
+ *     they stay in HBM, and a call records one HBH_STAGE_HASH entry, fallback or not.
+ *   Stages: the scaling and the sums under HBH_STAGE_CURVE; the Miller product, the closing pair, the
+ *     final exponentiation and the fallback under HBH_STAGE_PAIRING.
+ *   Width: hbh_engine_set_pairing_impl forced to HBH_IMPL_PAIR, _QUAD or _OCT is honoured by the Miller
+ *     product; any other forced value and HBH_IMPL_AUTO choose by lane-kernel slots, ceil(items / 2):
+ *     OCT up to HBH_AUTO_OCT_MAX slots, QUAD up to HBH_AUTO_QUAD_MAX, PAIR above.  Those thresholds were
+ *     measured for the full check; swept for this kernel at 1,024, 10,100 and 65,536 items (all valid,
+ *     pairing stage: OCT 5.3 / 5.5 ms against QUAD 6.3 and PAIR 9.2-9.3 at the first two, PAIR 10.7 and QUAD
+ *     10.8-11.1 against OCT 15.9 at the third; tools/batched_bench.py, profiles/r25/README.md) the ladder
+ *     picks the fastest width at each, so the kernel has no HBH_AUTO_BATCH_* constants of its own; the
+ *     crossovers between were not swept.  A forced width also governs the fallback, as it governs any
+ *     pairing call; under AUTO the fallback runs as a pairing call of its size.
+ *   Infinities as in the unbatched calls, through a passed group as through the fallback: pk = O with
+ *     sig = O is valid, pk = O with sig != O is invalid (the group's sum then fails its check), the same
+ *     for U = O / W = O.
+ * Argument errors and n = 0 are as in the unbatched calls.  stats (may be NULL) as in the grouped share
+ * checks: groups = groups of at least two items, groups_passed, singles (0 or 1), fallback_items = the
+ * items of the failed groups plus the single.  Stateless: no _dev, pool or G2-set form, and no AUTO
+ * switch between the batched and the per-item call: the caller opts in.
+ * Op model per item (hbbft_amd/workcount.py batched_model, Fp products): per-item check about 19.4 k;
+ * batched about 10.8 k with no failed group (ratio 0.56; the pairing stage alone 0.32); a failed group
+ * pays both.  MEASURED on an MI355X (profiles/r25/README.md; a form wins a cell when the other's median
+ * exceeds its own by more than both cells' min-max spreads together) the batched call is NOT faster
+ * host-to-host at any swept size: it loses at 1,024 items (8.4 -> 17.3 ms) and at 10,100 items (signatures
+ * 18.2 -> 21.3 ms, ciphertexts 17.6 -> 20.8 ms all valid; more with bad groups) and ties at 65,536 (57.5 ->
+ * 59.9, 55.4 -> 55.0 ms).  HBH_STAGE_PAIRING falls as modelled in direction (8.1 -> 5.5 ms at 10,100, 21.6 ->
+ * 10.7 ms at 65,536), but HBH_STAGE_CURVE, which the unbatched call does not have, costs 5.5 ms flat up to
+ * 10,100 items (G2 sums 3.1-3.2 ms, G1 scaling 2.3 ms: one chain per lane on a device they do not fill) and
+ * 10.2-10.6 ms at 65,536; and at 1,024 items the lane kernels' Miller product alone (5.3 ms) is slower than
+ * the wave kernels' whole unbatched check (1.9 ms).  Use it only where a measurement of the caller's own
+ * sizes says otherwise.
+ *   hbh_dbg_pairing_product: out[g] = (prod_{i in group g} e(P_i, Q_i))^3 in hbh_dbg_pairing's 576-byte
+ *     format, one value per group of HBH_BATCH_GROUP items (a last group of one item included), through
+ *     the same Miller-product launch and product + final exponentiation, with no closing pair. */
+#define HBH_BATCH_GROUP 256
+int hbh_verify_signatures_batched(hbh_engine* eng, size_t n, const uint8_t* pks, const uint8_t* sigs,
+                                  const uint8_t* data, const size_t* offsets, const uint8_t* scalars,
+                                  uint8_t* verdicts, hbh_grouped_stats* stats);
+int hbh_verify_ciphertexts_uv_batched(hbh_engine* eng, size_t n, const uint8_t* u, const uint8_t* data,
+                                      const size_t* offsets, const uint8_t* w, const uint8_t* scalars,
+                                      uint8_t* verdicts, hbh_grouped_stats* stats);
+int hbh_dbg_pairing_product(hbh_engine* eng, size_t n, const uint8_t* p, const uint8_t* q, uint8_t* out);
+
 /* ---------------------------------------------------------------- host stage (CPU, no engine)
  * What the north star keeps on the host, batched over `threads` std::thread workers (0 = all
  * hardware threads).  Variable-length inputs are concatenated in `data` with n+1 ascending byte
