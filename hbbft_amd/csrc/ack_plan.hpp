@@ -110,3 +110,21 @@ inline void order_by_y(size_t n, const uint32_t* ys, std::vector<uint32_t>& orde
   for (size_t a = 0; a < n; a++) order[a] = (uint32_t)a;
   std::stable_sort(order.begin(), order.end(), [ys](uint32_t i, uint32_t j) { return ys[i] < ys[j]; });
 }
+
+// The plan of one Ack drain: with use_fd, plan_fd's rows in fd and the acks left to the Horner kernel
+// (fd.other) in order of y in `order`; without it, or when no row qualifies, no FD row and every ack in
+// `order`.  A caller that cannot run the FD kernels after all plans again with use_fd = false BEFORE it
+// uploads anything: fd and order are rebuilt from nothing on every call.
+inline void plan_drain(size_t n, const std::vector<uint32_t>& slot, const uint32_t* ys, int t, bool use_fd, FdPlan& fd,
+                       std::vector<uint32_t>& order) {
+  fd = FdPlan();
+  if (use_fd) plan_fd(n, slot, ys, t, fd);
+  if (fd.slot.empty()) {
+    fd = FdPlan();
+    return order_by_y(n, ys, order);
+  }
+  std::vector<uint32_t> oy(fd.other.size());
+  for (size_t k = 0; k < fd.other.size(); k++) oy[k] = ys[fd.other[k]];
+  order_by_y(oy.size(), oy.data(), order);
+  for (auto& o : order) o = fd.other[o];
+}

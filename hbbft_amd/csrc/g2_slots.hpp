@@ -1,6 +1,6 @@
 // Slot allocator of a device-resident G2 set (hbh_g2_set_*): which of the set's `capacity` slots hold
 // a prepared point.  Free slots are handed out lowest first, so a released slot is the next one
-// reused and a set that never fills stays dense from slot 0.  Plain C++, no HIP: engine.hip keeps one
+// reused and a set that never fills stays dense from slot 0.  Plain C++, no HIP: the engine (engine_impl.hpp) keeps one
 // per set under the engine lock, tests/test_g2_slots_host.py runs it on the CPU.
 #pragma once
 #include <stddef.h>

@@ -1054,7 +1054,7 @@ int hbh_fr_poly_eval(size_t npoly, size_t ncoef, const uint8_t* coeffs, size_t n
 
 }  // extern "C"
 
-// Not part of the public ABI (engine.hip's split master check of hbh_combine_verify_g2): neg_out = -pk
+// Not part of the public ABI (engine_curve.hip's split master check of hbh_combine_verify_g2): neg_out = -pk
 // for the ABI point pk (infinity stays all-zero).
 extern "C" int hbh__host_g1_neg(const uint8_t* pk, uint8_t* neg_out) {
   hh::Jac<hh::Fq> p;
@@ -1063,7 +1063,7 @@ extern "C" int hbh__host_g1_neg(const uint8_t* pk, uint8_t* neg_out) {
   return HBH_OK;
 }
 
-// Not part of the public ABI (engine.hip's device form of hash_g2 / hash_g1_g2): the host half of the
+// Not part of the public ABI (engine_hash.hip's device form of hash_g2 / hash_g1_g2): the host half of the
 // hash -- seeds[i] = sha3_256 of message i, or of hash_g1_g2's message for (u_i, message i) when u is
 // given -- and the curve half from a seed, for the messages the device leaves to the host stage:
 // out[which[k]] = G2::rand(ChaChaRng::from_seed(seeds[which[k]])).

@@ -1,7 +1,7 @@
 // Host-side launchers of the HIP kernels.  Each kernel family lives in its own translation unit
 // (k_pair.hip, k_quad_g*.hip, k_oct_g*.hip, k_wave.hip, k_curve.hip, k_g1quad.hip, k_interp_pair.hip, k_wire.hip, k_rlc.hip, k_rlc_digits.hip) so the Makefile
-// compiles them in parallel; engine.hip owns the C ABI, device buffers and streams and calls only
-// these functions.  Its host arithmetic and planning live in host_fr.hpp, wire_host.hpp and ack_plan.hpp.
+// compiles them in parallel; the engine*.hip files (engine_impl.hpp) own the C ABI, device buffers and streams
+// and call only these functions.  Their host arithmetic and planning live in host_fr.hpp, wire_host.hpp and ack_plan.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

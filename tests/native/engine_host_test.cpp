@@ -9,6 +9,7 @@
 //   order n y...               -> the permutation
 //   dedup nack nparts (part x)... -> ok; nrow; row_part; row_x; row_of
 //   planfd n t (slot y)...     -> nfd; slot; y0; off; len; npts; epos (n); |fd_acks|; fd_acks; |other|; other
+//   plandrain n t use_fd (slot y)... -> plan_drain's plan as planfd prints it, |epos| before epos; |order|; order
 #include <cstdint>
 #include <cstdio>
 #include <iostream>
@@ -25,6 +26,20 @@ void put(uint64_t v) { std::printf("%llx ", (unsigned long long)v); }
 void put4(const uint64_t* w) { std::printf("%016llx%016llx%016llx%016llx ", (unsigned long long)w[3], (unsigned long long)w[2], (unsigned long long)w[1], (unsigned long long)w[0]); }
 void put_vec(const std::vector<uint32_t>& v) {
   for (uint32_t x : v) put(x);
+}
+void put_plan(const FdPlan& P, bool epos_len) {
+  put(P.slot.size());
+  put_vec(P.slot);
+  put_vec(P.y0);
+  put_vec(P.off);
+  put_vec(P.len);
+  put(P.npts);
+  if (epos_len) put(P.epos.size());
+  put_vec(P.epos);
+  put(P.fd_acks.size());
+  put_vec(P.fd_acks);
+  put(P.other.size());
+  put_vec(P.other);
 }
 bool get4(std::istream& in, uint64_t* w) {  // a scalar of up to 64 hex digits
   std::string h;
@@ -116,17 +131,21 @@ int main() {
       if (!in) return 2;
       FdPlan P;
       plan_fd(n, slot, ys.data(), t, P);
-      put(P.slot.size());
-      put_vec(P.slot);
-      put_vec(P.y0);
-      put_vec(P.off);
-      put_vec(P.len);
-      put(P.npts);
-      put_vec(P.epos);
-      put(P.fd_acks.size());
-      put_vec(P.fd_acks);
-      put(P.other.size());
-      put_vec(P.other);
+      put_plan(P, false);
+    } else if (cmd == "plandrain") {
+      size_t n = 0;
+      int t = 0, use_fd = 0;
+      in >> n >> t >> use_fd;
+      std::vector<uint32_t> slot(n), ys(n);
+      for (size_t a = 0; a < n; a++) in >> slot[a] >> ys[a];
+      if (!in) return 2;
+      FdPlan P;  // a used plan and order going in: plan_drain starts from nothing
+      std::vector<uint32_t> order(3, 0xdeadbeefu);
+      plan_fd(n, slot, ys.data(), t, P);
+      plan_drain(n, slot, ys.data(), t, use_fd != 0, P, order);
+      put_plan(P, true);
+      put(order.size());
+      put_vec(order);
     } else {
       return 2;
     }

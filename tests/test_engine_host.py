@@ -170,19 +170,22 @@ def test_dedup_rows(run):
     assert good[2 + 2 * n:] == [first[pa] for pa in acks]
 
 
-def parse_plan(row, n):
+def parse_plan(row, n=None):
+    """planfd's row for n acks; plandrain's (n = None): epos with its length, and the order at the end"""
     it = iter(row)
     take = lambda k: [next(it) for _ in range(k)]
     (nfd,) = take(1)
     plan = {"slot": take(nfd), "y0": take(nfd), "off": take(nfd), "len": take(nfd), "npts": take(1)[0],
-            "epos": take(n)}
+            "epos": take(take(1)[0] if n is None else n)}
     plan["fd_acks"] = take(take(1)[0])
     plan["other"] = take(take(1)[0])
+    if n is None:
+        plan["order"] = take(take(1)[0])
     assert not list(it)
     return plan
 
 
-def test_plan_fd(run):
+def fd_cases():
     rng = random.Random(5)
     fixed = [(0, y) for y in range(1, 9)] + [(1, 3), (1, 900)]
     cases = [(1, fixed), (128, [(0, y) for y in range(1, 600)])]  # t + 1 > 128: no FD row
@@ -194,7 +197,17 @@ def test_plan_fd(run):
             acks += [(slot, y) for y in ys] + [(slot, y) for y in ys[:2]]  # some y twice
         rng.shuffle(acks)
         cases.append((t, acks))
-    rows = run(["planfd %x %x %s" % (len(a), t, hexes(v for sy in a for v in sy)) for t, a in cases])
+    return cases
+
+
+def plan_lines(cmd, cases):
+    return ["%s %x %s %s" % (cmd, len(a), " ".join("%x" % v for v in head), hexes(v for sy in a for v in sy))
+            for head, a in cases]
+
+
+def test_plan_fd(run):
+    cases = fd_cases()
+    rows = run(plan_lines("planfd", [((t,), a) for t, a in cases]))
     plans = [parse_plan(row, len(a)) for (t, a), row in zip(cases, rows)]
 
     p = plans[0]  # slot 0: y = 1..8 from y0 = 0 (9 points); slot 1: too sparse
@@ -218,3 +231,33 @@ def test_plan_fd(run):
         assert p["len"] == sorted(p["len"], reverse=True)
         assert p["off"] == [sum(p["len"][:f]) for f in range(len(p["len"]))] and p["npts"] == sum(p["len"])
     assert any(p["slot"] and p["other"] for p in plans[2:])  # the random cases take both paths
+
+
+def test_plan_drain(run):
+    """plan_drain on planfd's cases, on one where every ack is an FD ack and on an empty drain: with use_fd
+    and at least one FD row the plan is plan_fd's and `order` the stable y order of the acks it leaves to the
+    Horner kernel; without use_fd, or with no FD row, the plan is empty and `order` the stable y order of
+    every ack, whatever fd and order held before."""
+    cases = fd_cases() + [(1, [(0, y) for y in range(1, 9)] + [(3, y) for y in range(40, 52)]),  # no ack left over
+                          (2, [])]
+    rows = run(plan_lines("planfd", [((t,), a) for t, a in cases]) +
+               plan_lines("plandrain", [((t, 1), a) for t, a in cases]) +
+               plan_lines("plandrain", [((t, 0), a) for t, a in cases]))
+    k = len(cases)
+    for i, (t, acks) in enumerate(cases):
+        n = len(acks)
+        want, fd, plain = parse_plan(rows[i], n), parse_plan(rows[k + i]), parse_plan(rows[2 * k + i])
+        by_y = lambda idx: sorted(idx, key=lambda a: acks[a][1])  # sorted() is stable
+        if want["slot"]:
+            assert {name: fd[name] for name in want} == want
+        else:  # no row qualifies: the plan is as empty as without use_fd
+            assert fd == plain
+        assert sorted(fd["order"] + fd["fd_acks"]) == list(range(n)) and sorted(fd["order"]) == want["other"]
+        assert fd["order"] == by_y(want["other"])
+        assert plain["order"] == by_y(range(n))
+        assert all(plain[name] == [] for name in ("slot", "y0", "off", "len", "epos", "fd_acks", "other"))
+        assert plain["npts"] == 0
+    plans = [parse_plan(row) for row in rows[k:2 * k]]
+    assert plans[1]["slot"] == [] and plans[1]["order"] == list(range(599))  # no FD row: every ack in order
+    assert plans[-2]["slot"] and plans[-2]["order"] == []                    # every ack an FD ack
+    assert any(p["slot"] and p["order"] for p in plans)

@@ -1,5 +1,5 @@
 """The slot allocator of resident G2 sets (hbbft_amd/csrc/g2_slots.hpp, used by hbh_g2_set_add /
-hbh_g2_set_release in engine.hip): a stand-alone host program includes the header and checks
+hbh_g2_set_release in engine_pairing.hip): a stand-alone host program includes the header and checks
 
 * free slots are handed out lowest first;
 * a released slot is the next one reused;
@@ -100,9 +100,14 @@ def test_slot_allocator(slots_program):
 
 
 def test_engine_uses_the_header():
-    """The sets of engine.hip allocate through the header under test."""
-    with open(os.path.join(CSRC, "engine.hip")) as f:
+    """The sets of the engine (the struct in engine_impl.hpp, the calls in engine_pairing.hip) allocate
+    through the header under test."""
+    with open(os.path.join(CSRC, "engine_impl.hpp")) as f:
         text = f.read()
     assert '#include "g2_slots.hpp"' in text
-    for use in ("G2Slots slots", "slots.take(", "slots.release(", "slots.live("):
+    assert "G2Slots slots" in text
+    with open(os.path.join(CSRC, "engine_pairing.hip")) as f:
+        text = f.read()
+    assert '#include "engine_impl.hpp"' in text
+    for use in ("slots.take(", "slots.release(", "slots.live("):
         assert use in text, use

@@ -1,4 +1,4 @@
-"""The call contract of the C ABI's engine entry points (hbbft_amd/csrc/engine.hip), pinned on the raw
+"""The call contract of the C ABI's engine entry points (hbbft_amd/csrc/engine*.hip), pinned on the raw
 ctypes binding: every argument error's code and message, the order of the checks where two apply,
 zero-size calls, a detached commitment set, and the stage accounting of hbh_engine_stage_time.  A bad
 call must leave the engine usable: correct results follow on the same engine."""

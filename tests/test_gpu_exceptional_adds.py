@@ -57,7 +57,7 @@ T = D.T
 G1 = g1a(C.g1_uncompressed(C.G1_GEN))
 G2 = g2a(C.g2_uncompressed(C.G2_GEN))
 O1, O2 = bytes(96), bytes(192)
-INTERP_PAIR_MAX, INTERP_G1Q_MAX = 384, 256  # engine.hip: the latency forms run up to these many combines
+INTERP_PAIR_MAX, INTERP_G1Q_MAX = 384, 256  # engine_curve.hip: the latency forms run up to these many combines
 
 
 def g1(k):

@@ -18,6 +18,7 @@ from hbbft_amd import _lib, hoststage
 from hbbft_amd.sync_key_gen import G1_GEN
 from oracle import bls12_381 as C
 from oracle import tc
+from tests.hash_trials import candidates, trial  # noqa: F401 (test_gpu_hash_quad imports them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,28 +26,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NTRIAL = 2000
 
 
-def trial(i):
-    return b"hbh-trial-%d" % i
-
-
 def abi_g2(pt):
     (x0, x1), (y0, y1) = pt
     return b"".join(v.to_bytes(48, "little") for v in (x0, x1, y0, y1))
-
-
-def candidates(msg):
-    """how many x G2::rand draws for msg before x^3 + b is a square: a in Fq2 is a square iff its norm
-    is a square in Fq"""
-    rng = tc.ChaChaRng(tc.sha3_256(msg))
-    k = 0
-    while True:
-        k += 1
-        x = (rng.gen_fq(), rng.gen_fq())
-        rng.gen_bool()
-        a = C.f2_add(C.f2_mul(C.f2_sqr(x), x), C.B2)
-        nrm = (a[0] * a[0] + a[1] * a[1]) % C.P
-        if nrm == 0 or pow(nrm, (C.P - 1) // 2, C.P) == 1:
-            return k
 
 
 @pytest.fixture(scope="module")

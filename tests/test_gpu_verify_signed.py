@@ -12,6 +12,7 @@ from hbbft_amd.dynamic_honey_badger import (DhbKeyGen, SignedKeyGenMsg, SignedVo
                                             encryption_schedule, node_change, vote_bytes)
 from hbbft_amd.sync_key_gen import G1_GEN, G2_GEN, R_ORDER, SyncKeyGen
 from oracle import cbls
+from tests.hash_trials import candidates, trial
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +23,7 @@ def dev(engine):
     engine.set_profiling(True)
     yield engine
     engine.set_profiling(False)
+    engine.dbg_set_hash_rounds(0)
     engine.set_hash_impl(_lib.HASH_AUTO)
 
 
@@ -62,6 +64,35 @@ def test_verify_signed_matches_host_hashed_verdicts(dev):
     assert dev.verify_signed(pks, sigs, msgs) == got
     assert hash_launches(dev) == 0
     assert dev.verify_signed([], [], []) == b""
+
+
+def test_round_cap_leftovers_are_patched_into_the_hash_table(dev):
+    """With the sampler capped at two rounds the device leaves every message of more than two candidates
+    to the host stage, whose hashes are patched into the Q1 table in HBM before the pairing check reads
+    it.  An unpatched entry is the all-zero point: a valid signature's verdict would turn to 0."""
+    rng = random.Random(159)
+    n, nkeys = 65, 5  # one full wave plus one item
+    msgs = [trial(i) for i in range(300, 300 + n)]
+    cand = [candidates(m) for m in msgs]
+    left = [i for i, c in enumerate(cand) if c > 2]
+    assert len(left) >= 5 and n - len(left) >= 5
+    assert 10 in left and 0 not in left  # the two corrupted positions: one patched, one resolved
+    sks = [rng.randrange(1, R_ORDER) for _ in range(nkeys)]
+    keys = hoststage.g1_mul([G1_GEN] * nkeys, sks)
+    hs = hoststage.hash_g2(msgs)
+    signer = [i % nkeys for i in range(n)]
+    sigs = hoststage.g2_mul(hs, [sks[j] for j in signer])
+    pks = [keys[j] for j in signer]
+    for i in (0, 10):  # a signature over another message
+        sigs[i] = hoststage.g2_mul([hs[i + 1]], [sks[signer[i]]])[0]
+    dev.dbg_set_hash_rounds(2)
+    got = dev.verify_signed(pks, sigs, msgs)
+    assert hash_launches(dev) == 1
+    dev.set_hash_impl(_lib.HASH_HOST)
+    dev.set_profiling(True)
+    assert got == dev.verify_signed(pks, sigs, msgs)
+    assert hash_launches(dev) == 0
+    assert list(got) == [0 if i in (0, 10) else 1 for i in range(n)]
 
 
 def key_gen_run(engine, device_hash):

@@ -35,8 +35,8 @@ def test_auto_range_is_empty_or_inside_the_wave_kernels_sizes():
 
 
 def test_engine_dispatches_the_kind():
-    eng = read("hbbft_amd", "csrc", "engine.hip")
+    eng = read("hbbft_amd", "csrc", "engine_pairing.hip")
     assert "hbl::wavep_verify(" in eng
     assert eng.count("HBH_AUTO_WAVEP_MIN") >= 2 and eng.count("HBH_AUTO_WAVEP_MAX") >= 2  # resolve_impl, verify_auto
-    assert "impl != HBH_IMPL_WAVEP" in eng  # accepted by the setter
+    assert "impl != HBH_IMPL_WAVEP" in read("hbbft_amd", "csrc", "engine.hip")  # accepted by the setter
     assert "$(BUILD)/k_wavep.o" in read("hbbft_amd", "Makefile")
